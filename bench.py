@@ -11,8 +11,12 @@ A "step" is one pass of the reference loop body (model/helper_functions.py:577-6
 batch: zero_grad, log-Mel front-end of 8 labelled + 8 unlabelled 327 680-sample segments, VAT power
 iteration on both, transcriber -> reconstructor -> transcriber, the 11 losses, backward, [gradient
 all-reduce], Adam + StepLR, post-step gradient clip.  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line; at N=1 it also carries the conv-phase roofline (measured with HIP events on
-the launch stream) and the CPU baseline (the oracle timed on the host cores, bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line; with
+--full (N=1, headline workload) the line also carries the conv-phase roofline (measured with HIP events on
+the launch stream), the deterministic-mode and data-parallel-seam timings, the parity leg against the
+reference fixture and the CPU baseline (the oracle timed on the host cores, bounded sample).
+Every step starts from the seeded initial weights, so the results of a step depend only on the arguments;
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs()).
 """
 import argparse
 import json
@@ -674,6 +678,37 @@ def make_rank_step(model_name, batch_l, batch_ul_n, rank, device, graph=True, du
     return model, opt, batch, batch_ul, step
 
 
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, step, opt, model):
+    """What a caller of the timed step holds after its LAST step, as out_dir/<name>.npy (float32): the weighted loss (`loss`), the
+    11 loss terms (`loss_<term>`), the updated parameters (`params`: the flat fp32 bucket, FlatAdam layout) and their clipped
+    gradients (`grads`, same layout), and the BatchNorm running means / variances in named_buffers() order (`bn_running_stats`).
+    Together ~29 MB for the bench workloads (the parameter bucket and its gradients dominate; the batch size does not enter); a model
+    whose dump would exceed DUMP_LIMIT_BYTES is refused before anything is written.
+    Every step starts from the seeded initial weights (main()), so two runs with the same arguments write the same values: the loss
+    terms and running statistics bit for bit, the gradients and parameters up to the order of the fp32 atomic gradient folds."""
+    import re
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {'loss': step.loss}
+    for k, v in step.losses.items():
+        arrays['loss_' + re.sub(r'[^A-Za-z0-9_]', '_', k.split('/')[-1])] = v
+    arrays['params'] = opt.flat_param
+    arrays['grads'] = opt.flat_grad
+    stats = [b.reshape(-1) for n, b in model.named_buffers() if n.rsplit('.', 1)[-1] in ('running_mean', 'running_var')]
+    if stats:
+        arrays['bn_running_stats'] = torch.cat(stats)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f'--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -685,13 +720,20 @@ def main():
     ap.add_argument('--batch-l', type=int, default=None, help='labelled segments per GPU (default: --batch)')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
     ap.add_argument('--single-stream', action='store_true', help='disable the two-stream step schedule (A/B)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline measurement (one GPU, headline workload): the conv-phase roofline and per-family table, the '
+                         'deterministic-mode and data-parallel-seam timings, the parity leg and the CPU baseline (each still switched '
+                         'off by its --no-* option); a plain run measures the headline figure only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (losses, parameters, gradients, BatchNorm '
+                         'running statistics) as DIR/<name>.npy, float32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--bf16-backward', action='store_true',
                     help='BASELINE config 3 as an opt-in experiment (NOT the headline): bf16 operands in the backward 3x3 convs of the final '
                          'graphs; every forward pass and the power iteration stay fp32 (loss terms / posteriorgrams unchanged)')
     ap.add_argument('--no-parity', action='store_true', help='skip the post-run parity leg (frozen-weight step vs the reference fixture)')
-    ap.add_argument('--verbose', action='store_true', help='dump the per-launch conv table to stderr')
+    ap.add_argument('--verbose', action='store_true', help='dump the per-launch conv table to stderr (with --full)')
     ap.add_argument('--dp-dump', default=None, metavar='DIR',
                     help='test instrumentation (tests/test_dp_gpu.py): every rank writes DIR/rank<r>.pt -- its data / VAT-noise checksums, its '
                          'gradient bucket before and after the FIRST all-reduce and its parameters after the first optimiser step')
@@ -755,16 +797,31 @@ def main():
                 dump['params_after_step1'] = opt.flat_param.detach().cpu().clone()
                 dump['losses_step1'] = {k: float(v) for k, v in step.losses.items()}
 
+    # Every step -- warm-up and timed -- trains from the seeded initial weights: the parameters are restored and repacked before it.
+    # The parameter gradients are folded with fp32 atomics (ops.DETERMINISTIC), and a chain of Adam steps would amplify those last-bit
+    # differences into run-to-run differences of every later loss and gradient; from fixed weights each step -- the last one too, whose
+    # results --dump-outputs writes -- computes the same values in every run.  So the losses of the line are those of the initial weights
+    # (at the step's own VAT noise draw); the Adam moments, step count and BatchNorm running statistics carry on from step to step, and the
+    # parameters after a step are the initial ones plus that step's update.  The restore is not part of the workload: in the timed loop
+    # it sits between two HIP events of its own, and its device time is taken out of every figure of the line (`weight_restore_ms_per_step`).
+    init_params = opt.flat_param.clone()
+
+    def restore():
+        opt.flat_param.copy_(init_params)
+        # (the plan is None only before the first eager step, when the parameters still are init_params: nothing to repack)
+        if step.pack_plan is not None:
+            step.pack_plan.run()
+
     for i in range(args.warmup):
+        restore()
         step()
         if dump is not None and i == 0:
             grab_params()
     barrier()
-    # K + 1 HIP events on the launch stream: event i sits behind step i, so consecutive differences are the per-step device times
-    # (`ms_per_step` = their median; the barrier-to-barrier wall clock of the same K steps stays the basis of `value`)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    ev0, ev1 = evs[0], evs[-1]
-    ev0.record()
+    # HIP events on the launch stream around every restore and every step: the step intervals are the per-step device times (SURVEY 8(d):
+    # `ms_per_step` = their median); the barrier-to-barrier wall clock of the same K steps, less the restores' device time, stays the
+    # basis of `value`
+    ev_r, ev_s, ev_e = ([torch.cuda.Event(enable_timing=True) for _ in range(args.steps)] for _ in range(3))
     t0 = time.perf_counter()
     # test instrumentation (tests/test_dp_gpu.py): this rank dies in the middle of the timed loop -- its peers are then blocked in the
     # next collective and it is the LAUNCHER's job to notice, terminate them and exit non-zero
@@ -773,14 +830,18 @@ def main():
         if fail_at is not None and i == fail_at:
             torch.cuda.synchronize()
             os._exit(17)
+        ev_r[i].record()
+        restore()
+        ev_s[i].record()
         step()
-        evs[i + 1].record()
+        ev_e[i].record()
         if dump is not None and i == 0:
             grab_params()
     barrier()
-    elapsed = time.perf_counter() - t0
-    device_ms = ev0.elapsed_time(ev1)             # the same K steps on the device's own clock (HIP events on the launch stream)
-    per_step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
+    restore_ms = sum(ev_r[i].elapsed_time(ev_s[i]) for i in range(args.steps))
+    elapsed = time.perf_counter() - t0 - restore_ms * 1e-3
+    device_ms = ev_r[0].elapsed_time(ev_e[-1]) - restore_ms      # the same K steps on the device's own clock (HIP events on the launch stream)
+    per_step_ms = sorted(ev_s[i].elapsed_time(ev_e[i]) for i in range(args.steps))
     median_ms = per_step_ms[len(per_step_ms) // 2] if len(per_step_ms) % 2 else 0.5 * (per_step_ms[len(per_step_ms) // 2 - 1] + per_step_ms[len(per_step_ms) // 2])
     if dp.active():
         t = torch.tensor([elapsed, median_ms], device=device, dtype=torch.float64)
@@ -805,6 +866,8 @@ def main():
                     names=[n for n, p_ in model.named_parameters() if p_.requires_grad])
         os.makedirs(args.dp_dump, exist_ok=True)
         torch.save(dump, os.path.join(args.dp_dump, f'rank{rank}.pt'))
+    if args.dump_outputs and rank == 0:           # (before the --full legs, which run further steps on the same model)
+        dump_outputs(args.dump_outputs, step, opt, model)
     ms = elapsed / args.steps * 1e3
     assert _lib_mod.load().rv_source_digest().decode() == _lib_mod.source_digest(), 'stale libreconvat_hip.so'
     audio_s = world * (batch_l + args.batch) * SEG_SECONDS * args.steps / elapsed
@@ -828,6 +891,8 @@ def main():
                    'final_loss': round(loss, 5), 'vat_nan_flag': nan_flag, 'losses_last_step': loss_terms},
         # the same K steps timed by two HIP events on the launch stream (the record carries its own evidence that the device worked)
         'device_ms_per_step': round(device_ms / args.steps, 3),
+        # device time of the weight restore before each timed step (not part of any figure above)
+        'weight_restore_ms_per_step': round(restore_ms / args.steps, 3),
         'dp_ranks': dp_ranks, 'dp_backend': (dist.get_backend() if dp.active() else None), 'replicas_equal': replicas_equal,
         'param_checksum': int(checksum.item()),
         # gradient all-reduces issued by FlatAdam.step (RCCL, or gloo through pinned host memory): one per optimiser step
@@ -837,7 +902,7 @@ def main():
         'device_memory_gb': {'max_allocated': round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2),
                              'max_reserved': round(torch.cuda.max_memory_reserved(device) / 2 ** 30, 2)},
     }
-    if rank == 0 and world == 1 and args.model == 'onset' and batch_l == args.batch == 8:       # (the roofline / parity legs are written for the headline workload)
+    if args.full and rank == 0 and world == 1 and args.model == 'onset' and batch_l == args.batch == 8:     # (written for the headline workload)
         if not args.no_roofline:
             eager = ra.TrainStep(model, opt, batch, batch_ul, alpha=1.0, VAT=True, clip=3.0, graph=False, bf16_backward=args.bf16_backward)
             conv_ms, conv_flops_total, per_kernel, nlaunch, min_sets, bound = measure_conv_phase(eager, device)

@@ -212,22 +212,28 @@ def test_bench_self_launch_two_ranks(dev):
     assert line['n_gpus'] == 2 and line['dp_ranks'] == 2 and line['dp_backend'] == 'nccl' and line['replicas_equal'] is True
 
 
-def test_rccl_allreduce_executes_on_one_gpu(dev):
+def test_rccl_allreduce_executes_on_one_gpu(dev, tmp_path):
     """The builder's lease is ONE GPU and RCCL refuses two ranks on one device ("Duplicate GPU detected"), so the two-rank test
     above skips there.  This one runs the data-parallel code path for real with a SINGLE-rank RCCL group (RV_DP_FORCE_ALLREDUCE=1):
     `init_process_group('nccl')`, the barrier, FlatAdam's one `dist.all_reduce` of the 14.6 MB flat bucket per step between the
     hipGraph replay and the Adam kernel, the MAX / MIN reductions of the replica check, the teardown -- and the step must still
-    train (same loss as without the group; an all-reduce over one rank is the identity)."""
-    outs = []
+    train (same loss, gradients and Adam-updated parameters as without the group; an all-reduce over one rank is the identity).
+    Every bench step trains from the seeded initial weights, so the loss alone does not see the all-reduced bucket: the gradients and
+    the parameters after the last Adam step (--dump-outputs) do."""
+    import numpy as np
+    outs, dumps = [], []
     for force in ('0', '1'):
         env = dict(os.environ, PYTHONPATH=ROOT, RV_DP_FORCE_ALLREDUCE=force, HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_PORT='29547')
+        out = str(tmp_path / f'force{force}')
         p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                            '--no-roofline', '--no-parity'], capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
+                            '--no-roofline', '--no-parity', '--dump-outputs', out], capture_output=True, text=True, cwd=ROOT, env=env,
+                           timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
         assert len(lines) == 1, p.stdout[-2000:]
         assert p.stdout.strip().splitlines()[-1] == lines[0], 'the JSON line must be the LAST line of stdout: ' + p.stdout[-1500:]
         outs.append(json.loads(lines[0]))
+        dumps.append({k: np.load(os.path.join(out, k + '.npy')) for k in ('params', 'grads')})
     plain, rccl = outs
     # the line's own contract (SURVEY 8(d), round 6): `ms_per_step` = the median of the per-step device times, `value` = whole-job throughput over the
     # barrier-to-barrier wall clock (`mean_ms_per_step`), and the library's source digest equals the digest of the sources next to it
@@ -239,6 +245,18 @@ def test_rccl_allreduce_executes_on_one_gpu(dev):
     assert plain['dp_allreduce_calls'] == 0 and rccl['dp_allreduce_calls'] == 4 and rccl['dp_ranks'] == 1 and rccl['dp_backend'] == 'nccl'
     assert rccl['replicas_equal'] is True
     assert abs(rccl['config']['final_loss'] - plain['config']['final_loss']) <= 2e-3 * abs(plain['config']['final_loss'])
+    # the bucket that came back from the collective (clipped, as the step leaves it) and what Adam made of it
+    for k in ('grads', 'params'):
+        a, b = dumps[0][k].astype(np.float64), dumps[1][k].astype(np.float64)
+        assert np.abs(a).max() > 0 and np.abs(a - b).max() <= 1e-5 * np.abs(a).max(), (k, float(np.abs(a - b).max()))
+    # ... and Adam did move the parameters away from the seeded initial weights (lr 1e-3: most entries move by ~1e-3)
+    import bench
+    _, opt0, _, _, step0 = bench.make_rank_step('onset', 8, 8, 0, dev, graph=False)
+    init = opt0.flat_param.cpu().numpy().astype(np.float64)
+    del step0, opt0
+    for d in dumps:
+        moved = np.abs(d['params'].astype(np.float64) - init)
+        assert np.median(moved[init != 0]) > 1e-4, float(np.median(moved[init != 0]))
 
 
 def test_bench_refuses_more_gpus_than_present(dev):
@@ -246,3 +264,43 @@ def test_bench_refuses_more_gpus_than_present(dev):
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '1', '--warmup', '0'],
                        capture_output=True, text=True, cwd=ROOT, timeout=300)
     assert p.returncode != 0 and 'exposes' in p.stderr
+
+
+def test_bench_plain_line_and_dump_outputs(dev, tmp_path):
+    """A plain `python bench.py` (headline workload) measures the headline figure only -- the roofline, parity, deterministic, seam
+    and CPU legs run with --full -- and --dump-outputs writes what the last timed step computed: float32 arrays, at most 64 MiB in
+    all, whose loss terms are the line's `losses_last_step` and whose parameters carry the line's `param_checksum`.  Two runs with
+    the same arguments write the same values: the loss terms and running statistics bit for bit, the gradients and parameters up to
+    the order of the fp32 atomic gradient folds."""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    dumps = []
+    for run_ in ('a', 'b'):
+        out = str(tmp_path / run_)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2',
+                            '--dump-outputs', out], capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 3 and line['warmup'] == 2 and line['optimizer_steps'] == 5 and line['ms_per_step'] > 0
+        assert not {'roofline', 'parity', 'cpu_baseline', 'deterministic_ms_per_step', 'dp_seam'} & set(line)
+        files = sorted(os.listdir(out))
+        assert all(f.endswith('.npy') for f in files) and {'loss.npy', 'params.npy', 'grads.npy', 'bn_running_stats.npy'} <= set(files)
+        arrays = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        terms = line['config']['losses_last_step']
+        assert len(terms) == 11 and len([k for k in arrays if k.startswith('loss_')]) == 11
+        for k, v in terms.items():
+            assert abs(float(arrays['loss_' + k.split('/')[-1]]) - v) <= 1e-5 * max(abs(v), 1.0), k
+        assert abs(float(arrays['loss']) - line['config']['final_loss']) <= 1e-4 * max(abs(line['config']['final_loss']), 1.0)
+        assert int(arrays['params'].view(np.int32).sum(dtype=np.int64)) == line['param_checksum']
+        assert np.isfinite(arrays['grads']).all() and arrays['grads'].shape == arrays['params'].shape
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for k in a:
+        if k.startswith('loss') or k == 'bn_running_stats':
+            assert np.array_equal(a[k], b[k]), k
+        else:
+            err = float(np.abs(a[k].astype(np.float64) - b[k]).max())
+            assert err <= 1e-5 * float(np.abs(a[k]).max()), (k, err)

@@ -1,4 +1,4 @@
-"""Aggregate the [conv] lines of `bench.py --verbose` by launch class.   python tools/conv_classes.py gpurun_out/x.log [N top rows]"""
+"""Aggregate the [conv] lines of `bench.py --full --verbose` by launch class.   python tools/conv_classes.py <stderr log> [N top rows]"""
 import collections
 import re
 import sys
