@@ -39,6 +39,17 @@ int rv_melspec_lognorm_fwd(const float* audio, long audio_stride, int B, int nsa
                            const float* twiddle, const int* mel_start, const int* mel_len, const float* mel_w, int mel_ld,
                            int n_mels, int hop, int do_log, int normalise, float* out, int T, void* workspace, void* stream);
 
+/* ---- constant-Q front end (nnAudio CQT1992v2 as the reference configures it, model/UNet_onset.py:346-349) ----------
+ * audio [B, nsamp] -> out [B, T, n_bins] time-major, T = 1 + nsamp/hop, reflect pad kernel_width/2 (nsamp must exceed it):
+ * |cqt| (do_log: log(|cqt| + 1e-5); normalise: per-clip min-max).  w / items / groups / scale are the packed tables of
+ * reconvat_amd.frontend.CQT1992v2.tables(): per 16-bin group the [32][K_g] taps of its window, split-K work items
+ * (group, first tap, taps, weight offset, K_g, 0, 0, 0), per group (first item, item count), sqrt(lengths).
+ * workspace: rv_cqt_workspace_bytes(B, nsamp, n_items, hop, kernel_width) bytes, 16-byte aligned. */
+long rv_cqt_workspace_bytes(int B, int nsamp, int n_items, int hop, int kernel_width);
+int rv_cqt_lognorm_fwd(const float* audio, long audio_stride, int B, int nsamp, const float* w, long w_floats, const int* items,
+                       int n_items, const int* groups, int n_groups, const float* scale, int n_bins, int kernel_width, int hop,
+                       int do_log, int normalise, float* out, int T, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- convolutions (nn.Conv2d / nn.ConvTranspose2d call sites, model/UNet_onset.py:173-224) ------
  * rv_pack_weights: PyTorch-layout weight -> MFMA fragment order for a logical Wm[tap][k][n]
  *   value(tap,k,n) = w[k*s_k + n*s_n + (flip ? taps-1-tap : tap)];  scatter_cmid>0: 2x2/s2 scatter GEMM.

@@ -24,6 +24,8 @@ SIGNATURES = {
     'rv_last_error': (ctypes.c_char_p, []),
     'rv_source_digest': (ctypes.c_char_p, []),
     'rv_melspec_lognorm_fwd': (I, [P, L, I, I, P, P, P, P, P, I, I, I, I, I, P, I, P, P]),
+    'rv_cqt_workspace_bytes': (L, [I, I, I, I, I]),
+    'rv_cqt_lognorm_fwd': (I, [P, L, I, I, P, L, P, I, P, I, P, I, I, I, I, I, P, I, P, L, P]),
     'rv_packed_weight_floats': (L, [I, I, I]),
     'rv_pack_weights': (I, [P, P, I, I, I, L, L, I, I, I, P]),
     'rv_pack_table_entry_bytes': (L, []),

@@ -20,8 +20,8 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from . import ops
-from .constants import N_BINS
-from .frontend import MelSpectrogram, Normalization
+from .constants import N_BINS, SAMPLE_RATE, HOP_LENGTH
+from .frontend import CQT1992v2, MelSpectrogram, Normalization
 from .ops import (ARENA, BnLink, ColsumLink, GradShare, ConvFn, UpCatFn, BnActFn, LinearFn, OnsetHeadsFn, LocalAttnFn, VatPerturbFn, SLOPE, bce_mean,
                   mse_mean, abs_mean)
 
@@ -213,22 +213,22 @@ class Stack(nn.Module):
 class Spec2Roll(nn.Module):
     """Transcriber.  onset=True: model/UNet_onset.py:284-315; onset=False: model/self_attention_VAT.py:929-945."""
 
-    def __init__(self, ds_ksize, ds_stride, complexity=4, onset=True):
+    def __init__(self, ds_ksize, ds_stride, complexity=4, onset=True, n_bins=N_BINS):
         super().__init__()
         self.onset = onset
         self.Unet1_encoder = Encoder(ds_ksize, ds_stride)
         self.Unet1_decoder = Decoder(ds_ksize, ds_stride, 2 if onset else 1)
         if onset:
-            self.lstm1 = MutliHeadAttention1D(N_BINS + 88, N_BINS * complexity, 31, position=True, groups=complexity)
-            self.linear1 = nn.Linear(N_BINS * complexity, 88)
-            self.linear_onset = nn.Linear(N_BINS, 88)
-            self.linear_feature = nn.Linear(N_BINS, 88)
+            self.lstm1 = MutliHeadAttention1D(n_bins + 88, n_bins * complexity, 31, position=True, groups=complexity)
+            self.linear1 = nn.Linear(n_bins * complexity, 88)
+            self.linear_onset = nn.Linear(n_bins, 88)
+            self.linear_feature = nn.Linear(n_bins, 88)
             self.dropout_layer = nn.Dropout(0.5)
             self.combine_stack = Stack(input_size=88 * 2, hidden_dim=768, attn_size=31, attn_group=6, output_dim=88,
                                        dropout=0)
         else:
-            self.lstm1 = MutliHeadAttention1D(N_BINS, N_BINS * complexity, 31, position=True, groups=complexity)
-            self.linear1 = nn.Linear(N_BINS * complexity, 88)
+            self.lstm1 = MutliHeadAttention1D(n_bins, n_bins * complexity, 31, position=True, groups=complexity)
+            self.linear1 = nn.Linear(n_bins * complexity, 88)
 
     def forward(self, x, detach=False):
         b, _, t, f = x.shape
@@ -245,17 +245,17 @@ class Spec2Roll(nn.Module):
 class Roll2Spec(nn.Module):
     """Reconstructor (model/UNet_onset.py:317-339)."""
 
-    def __init__(self, ds_ksize, ds_stride, complexity=4):
+    def __init__(self, ds_ksize, ds_stride, complexity=4, n_bins=N_BINS):
         super().__init__()
         self.Unet2_encoder = Encoder(ds_ksize, ds_stride)
         self.Unet2_decoder = Decoder(ds_ksize, ds_stride, 1)
-        self.lstm2 = MutliHeadAttention1D(88, N_BINS * complexity, 31, position=True, groups=4)
-        self.linear2 = nn.Linear(N_BINS * complexity, N_BINS)
+        self.lstm2 = MutliHeadAttention1D(88, n_bins * complexity, 31, position=True, groups=4)
+        self.linear2 = nn.Linear(n_bins * complexity, n_bins)
 
     def forward(self, x, detach=False):
         b, t, _ = x.shape
         z, a = self.lstm2(x, detach)
-        s = _linear(self.linear2, z, 1, detach)                    # sigmoid(linear2(.)) [B, T, 229]
+        s = _linear(self.linear2, z, 1, detach)                    # sigmoid(linear2(.)) [B, T, n_bins]
         y = _unet(self.Unet2_encoder, self.Unet2_decoder, s.unsqueeze(1), detach)
         return y.view(b, 1, t, y.shape[2]), a
 
@@ -348,9 +348,18 @@ class UNet_VAT(nn.Module):
 class _Base(nn.Module):
     def __init__(self, log, reconstruction, mode, spec, XI, eps):
         super().__init__()
-        if spec != 'Mel':
-            raise NotImplementedError("only spec='Mel' is on the MI355X hot path (the reference scripts' default)")
-        self.spectrogram = MelSpectrogram()
+        # spec='CQT' (the reference's constructor default, model/UNet_onset.py:342-352): 88 * 2 constant-Q bins from 27.5 Hz at
+        # 24 bins per octave, and every bin-sized layer is 176 wide.  The reference sets its module-global N_BINS for that
+        # (a Mel model built later in the same process then gets 176 bands); here the bin count is this instance's own.
+        if spec == 'CQT':
+            self.n_bins = 88 * 2
+            self.spectrogram = CQT1992v2(sr=SAMPLE_RATE, hop_length=HOP_LENGTH, n_bins=self.n_bins, fmin=27.5, bins_per_octave=24,
+                                         trainable=False)
+        elif spec == 'Mel':
+            self.n_bins = N_BINS
+            self.spectrogram = MelSpectrogram()
+        else:
+            raise NotImplementedError(f"spec={spec!r}: the MI355X hot path provides spec='Mel' and spec='CQT'")
         self.log = log
         self.normalize = Normalization(mode)
         self.reconstruction = reconstruction
@@ -469,9 +478,9 @@ class UNet_Onset(_Base):
     def __init__(self, ds_ksize, ds_stride, log=True, reconstruction=True, mode='imagewise', spec='CQT', device='cpu',
                  XI=1e-6, eps=1e-2):
         super().__init__(log, reconstruction, mode, spec, XI, eps)
-        self.transcriber = Spec2Roll(ds_ksize, ds_stride, onset=True)
+        self.transcriber = Spec2Roll(ds_ksize, ds_stride, onset=True, n_bins=self.n_bins)
         if reconstruction:
-            self.reconstructor = Roll2Spec(ds_ksize, ds_stride)
+            self.reconstructor = Roll2Spec(ds_ksize, ds_stride, n_bins=self.n_bins)
 
     def forward(self, x, _first=None):
         pianoroll, onset, a = self.transcriber(x) if _first is None else _first
@@ -568,9 +577,9 @@ class UNet(_Base):
     def __init__(self, ds_ksize, ds_stride, log=True, reconstruction=True, mode='imagewise', spec='CQT', device='cpu',
                  XI=1e-6, eps=1e-2):
         super().__init__(log, reconstruction, mode, spec, XI, eps)
-        self.transcriber = Spec2Roll(ds_ksize, ds_stride, onset=False)
+        self.transcriber = Spec2Roll(ds_ksize, ds_stride, onset=False, n_bins=self.n_bins)
         if reconstruction:
-            self.reconstructor = Roll2Spec(ds_ksize, ds_stride)
+            self.reconstructor = Roll2Spec(ds_ksize, ds_stride, n_bins=self.n_bins)
 
     def forward(self, x, _first=None):
         pianoroll, a = self.transcriber(x) if _first is None else _first

@@ -147,6 +147,8 @@ class OnsetsAndFrames_VAT_full(_Base):
 
     def __init__(self, input_features, output_features, model_complexity=48, log=True, mode='imagewise', spec='Mel', XI=1e-5,
                  eps=10, VAT_mode='all'):
+        if spec != 'Mel':
+            raise NotImplementedError("the Onsets&Frames baseline provides spec='Mel' only (the reference scripts' default)")
         super().__init__(log, False, mode, spec, XI, eps)
         model_size = model_complexity * 16
 
@@ -303,6 +305,8 @@ class Frame_stack_VAT(_Base):
 
     def __init__(self, input_features, output_features, model_complexity=48, log=True, mode='imagewise', spec='Mel', XI=1e-5,
                  eps=10, VAT_mode='all'):
+        if spec != 'Mel':
+            raise NotImplementedError("the Onsets&Frames baseline provides spec='Mel' only (the reference scripts' default)")
         super().__init__(log, False, mode, spec, XI, eps)
         model_size = model_complexity * 16
         self.vat_loss = stepwise_VAT_frame_stack(XI, eps, 1, VAT_mode)
@@ -345,6 +349,8 @@ class Onset_stack_VAT(_Base):
 
     def __init__(self, input_features, output_features, model_complexity=48, log=True, mode='imagewise', spec='Mel', XI=1e-5,
                  eps=10, VAT_mode='all'):
+        if spec != 'Mel':
+            raise NotImplementedError("the Onsets&Frames baseline provides spec='Mel' only (the reference scripts' default)")
         super().__init__(log, False, mode, spec, XI, eps)
         model_size = model_complexity * 16
         self.vat_loss = None

@@ -627,26 +627,54 @@ class BnLink:
         return self.ws is not None and self.z is not None and tuple(self.z.shape) == tuple(dx.shape)
 
 
-_wgrad_tuned = set()
+_wgrad_tuned = set()       # (taps, B, Hv, Wv, Ca, Cb): shapes whose partition this process has decided
 _wgrad_plans = {}          # (taps, B, Hv, Wv, Ca, Cb) -> (nw, wgs): what this process pinned in the library (tools/tune_plans.py dumps it)
+# The library keys its partition by (taps, B, Hv, Ca, Cb), without the row width Wv: shapes that differ only in width -- the same layer of a
+# 229-bin and of a 176-bin model -- share ONE library entry.  _wgrad_owner records which full shape last pinned each entry; a launch of another
+# width re-pins the entry to its own plan (or the library default) first, so no shape runs the partition decided for another width.
+_wgrad_owner = {}          # (taps, B, Hv, Ca, Cb) -> (taps, B, Hv, Wv, Ca, Cb)
+
+
+def _pin_wgrad(lib, full, plan):
+    """Pin `plan` ((nw, wgs); None = library default) for the full shape `full` and record it as the owner of its library entry."""
+    taps, bb, hv, _, ca, cb = full
+    if lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *(plan if plan is not None else (0, 0))) != 0:
+        return False
+    _wgrad_owner[(taps, bb, hv, ca, cb)] = full
+    return True
+
+
+def _repin_wgrad(lib, full):
+    """Before a launch of the shape `full`: if another width pinned the shared library entry since, restore this shape's plan.
+    Host-only (legal under hipGraph capture); a no-op while one width uses the entry, i.e. for every launch of a single model."""
+    taps, bb, hv, _, ca, cb = full
+    owner = _wgrad_owner.get((taps, bb, hv, ca, cb))
+    if owner is not None and owner != full:
+        _pin_wgrad(lib, full, _wgrad_plans.get(full))
 
 
 def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, s_a, s_b, flip):
     """Per-shape partition of the MFMA weight-gradient kernel (waves per workgroup x workgroups on the chip): the first eager
     call of a shape times the candidates (HIP events on the launch stream, scratch outputs) and pins the winner in the library
     (rv_conv_wgrad_set_plan); under hipGraph capture an untuned shape keeps the library default (8 waves, 256 workgroups)."""
-    key = (taps, bb, hv, ca, cb)
-    if not AUTOTUNE or key in _wgrad_tuned or ca * cb * taps <= 144 or ca == 1:
+    key = (taps, bb, hv, wv, ca, cb)
+    if not AUTOTUNE or ca * cb * taps <= 144 or ca == 1:
+        return
+    if key in _wgrad_tuned:
+        _repin_wgrad(lib, key)
         return
     if AUTOTUNE == 'table':
         # host-only (legal under hipGraph capture); runs before the first launch of the shape, i.e. never between a deferred
         # weight-gradient launch of that shape and its table flush
         _wgrad_tuned.add(key)
-        plan = plans.lookup_wgrad((taps, bb, hv, wv, ca, cb))
-        if plan is not None and lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *plan) == 0:
-            _wgrad_plans[(taps, bb, hv, wv, ca, cb)] = plan
+        plan = plans.lookup_wgrad(key)
+        if plan is not None and _pin_wgrad(lib, key, plan):
+            _wgrad_plans[key] = plan
+        else:
+            _repin_wgrad(lib, key)
         return
     if torch.cuda.is_current_stream_capturing():
+        _repin_wgrad(lib, key)
         return
     _wgrad_tuned.add(key)
     st = torch.cuda.current_stream()
@@ -677,8 +705,8 @@ def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, 
             t = dt if t is None else min(t, dt)
         if best is None or t < best:
             best, choice = t, (nw, wgs)
-    lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *choice)
-    _wgrad_plans[(taps, bb, hv, wv, ca, cb)] = choice
+    _pin_wgrad(lib, key, choice)
+    _wgrad_plans[key] = choice
     if best is not None:
         _tune_us[('wgrad', (taps, bb, hv, wv, ca, cb))] = best / 3 * 1e3
     if os.environ.get('RV_TUNE_LOG'):
@@ -782,14 +810,18 @@ def conv_wgrad_merged(items):
     n = len(items)
     if n == 1 or not same:
         return False
-    tkey = (taps, n * bb, hv, ca, cb)
+    tkey = (taps, n * bb, hv, wv, ca, cb)
     if AUTOTUNE and tkey not in _wgrad_tuned:
         # the partition of n * bb images: the table's entry (or the nearest batch's), else the one this process tuned for one pass -- never the
         # on-line tuner's timing launches (they read n * bb CONTIGUOUS images from the first segment)
         _wgrad_tuned.add(tkey)
-        plan = (plans.lookup_wgrad((taps, n * bb, hv, wv, ca, cb)) if AUTOTUNE == 'table' else None) or _wgrad_plans.get((taps, bb, hv, wv, ca, cb))
-        if plan is not None and lib.rv_conv_wgrad_set_plan(taps, n * bb, hv, ca, cb, *plan) == 0:
-            _wgrad_plans[(taps, n * bb, hv, wv, ca, cb)] = tuple(plan)
+        plan = (plans.lookup_wgrad(tkey) if AUTOTUNE == 'table' else None) or _wgrad_plans.get((taps, bb, hv, wv, ca, cb))
+        if plan is not None and _pin_wgrad(lib, tkey, tuple(plan)):
+            _wgrad_plans[tkey] = tuple(plan)
+        else:
+            _repin_wgrad(lib, tkey)
+    elif AUTOTUNE:
+        _repin_wgrad(lib, tkey)
     nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, n * bb, hv, ca, cb)
     ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
     us = (ctypes.c_void_p * n)(*[g[2].data_ptr() for g in geo])
@@ -1879,6 +1911,27 @@ def melspec(audio, tables, do_log, normalise, hop=512):
     call('rv_melspec_lognorm_fwd', ptr(audio), audio.stride(0), bb, nsamp, ptr(tables['window']), ptr(tables['twiddle']),
          ptr(tables['mel_start']), ptr(tables['mel_len']), ptr(tables['mel_w']), tables['mel_w'].shape[1], n_mels, hop,
          1 if do_log else 0, 1 if normalise else 0, ptr(out), t, ptr(ws), stream())
+    return out
+
+
+def cqtspec(audio, tables, do_log, normalise, hop=512):
+    """audio [B, nsamp] -> [B, T, n_bins] (time-major) log-CQT / CQT magnitude; see rv_cqt_lognorm_fwd."""
+    need_gpu(audio)
+    audio = audio.float()
+    if audio.stride(-1) != 1:
+        audio = audio.contiguous()
+    bb, nsamp = audio.shape
+    t = 1 + nsamp // hop
+    n_bins, kw = tables['scale'].numel(), tables['kernel_width']
+    if nsamp <= kw // 2:
+        raise ValueError(f'cqtspec: the signal ({nsamp} samples) must be longer than the reflect padding ({kw // 2} samples)')
+    items, groups, w = tables['items'], tables['groups'], tables['w']
+    out = torch.empty((bb, t, n_bins), device=audio.device, dtype=torch.float32)
+    nbytes = int(_lib.load().rv_cqt_workspace_bytes(bb, nsamp, items.shape[0], hop, kw))
+    ws = torch.empty((nbytes + 3) // 4, device=audio.device, dtype=torch.float32)
+    call('rv_cqt_lognorm_fwd', ptr(audio), audio.stride(0), bb, nsamp, ptr(w), w.numel(), ptr(items), items.shape[0], ptr(groups),
+         groups.shape[0], ptr(tables['scale']), n_bins, kw, hop, 1 if do_log else 0, 1 if normalise else 0, ptr(out), t, ptr(ws),
+         nbytes, stream())
     return out
 
 

@@ -38,7 +38,7 @@ for key, old in sorted(doc['wgrad'].items()):
     w = torch.randn(cb, ca, *{9: (3, 3), 1: (1, 1), 4: (2, 2)}[taps], device=dev)
     picks = {}
     for rnd in range(2):
-        ops._wgrad_tuned.discard((taps, nb, hv, ca, cb))
+        ops._wgrad_tuned.discard((taps, nb, hv, wv, ca, cb))
         ops.conv_wgrad(kind, x, dy, w, True)
         torch.cuda.synchronize()
         plan = ops._wgrad_plans.get((taps, nb, hv, wv, ca, cb))

@@ -3,6 +3,8 @@
 
     python transcribe_files.py with device=cuda:0 weight=runs/.../model-final.pt input=Application/Input output=Application/Output
 
+``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
+
 Inputs: 16 kHz mono 16-bit ``.wav`` files or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
 """
 import os
@@ -46,11 +48,14 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
 
 
 def main(argv):
-    cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output')
+    cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel')
     cfg.update(parse_cli(argv))
-    model = ra.UNet((2, 2), (2, 2), log=True, reconstruction=True, mode='imagewise', spec='Mel', device=cfg['device'])
-    if cfg['weight']:
-        model.load_state_dict(torch.load(cfg['weight'], map_location='cpu'))
+    state = torch.load(cfg['weight'], map_location='cpu') if cfg['weight'] else None
+    if state is not None:                       # the checkpoint's front-end buffers name its spectrogram
+        cfg['spec'] = 'CQT' if 'spectrogram.cqt_kernels_real' in state else 'Mel'
+    model = ra.UNet((2, 2), (2, 2), log=True, reconstruction=True, mode='imagewise', spec=cfg['spec'], device=cfg['device'])
+    if state is not None:
+        model.load_state_dict(state)
     model.to(cfg['device']).eval()
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
     transcribe2midi(files, model, cfg['device'], cfg['output'])
