@@ -264,6 +264,28 @@ int rv_maxpool_w2_dropout_bwd(const float* dy, const unsigned char* code, float*
 int rv_dropout(const float* x, float* y, unsigned char* code_out, const unsigned char* code_in, long n, float p, unsigned seed,
                const long* epoch, void* stream);
 
+/* ---- Thickstun CNN baseline (model/Thickstun_model.py) in its window-sharing form ------------------------------------------
+ * The reference cuts the padded spectrogram into one 229 x 25 window per frame (:57-59) and runs CNN_freq, CNN_time and the
+ * linear layer on that batch of windows (:30-35).  Here z2 = relu(CNN_freq) is computed once per padded frame and kept
+ * channels-last, z2 [B, 51, Tin + 2*pad, 128]; z3 = relu(CNN_time) is a GEMM over a Hankel view of z2, z3 [B, T, 51, N]
+ * with T = Tin + 2*pad - 24.  (pad = 12: run_on_batch's F.pad; pad = 0, Tin = 25: forward() on ready-made windows.)
+ *
+ * rv_thick_freq_fwd (:30, torch.relu(self.CNN_freq(x.unsqueeze(1)))): x [B, Tin, 229] time-major, w [128][128] (channel, tap:
+ *   the checkpoint's [128,1,128,1]), bias [128]; the 2*pad zero frames become relu(bias).
+ * rv_thick_freq_bwd (autograd of :30): dw [128][128], db [128] (accumulate: += ) from dz2, with the ReLU mask of z2 applied on
+ *   load; partial sums per 8 frames are added in a fixed order (no float atomics).  workspace: rv_thick_freq_bwd_workspace_bytes.
+ * rv_thick_tconv_fwd (:32, torch.relu(self.CNN_time(z2))): wj [25][N][128] = rv_pack_weights(plain, taps = 25, kdim = N,
+ *   ndim = 128, s_k = 3200, s_n = 25) of the checkpoint's [N,128,1,25]; bias [N]; N % 128 == 0; 16-byte aligned operands.
+ * rv_thick_linear_dz (autograd of :34, the gradient of self.linear's input through the ReLU of :32): dy [M, N] logit gradients,
+ *   wt [K, N] the linear weight transposed and in z3's feature order, z3 / dz3 [M, K]; dz3 = z3 > 0 ? dy @ wt^T : 0.
+ *   N <= 96, N % 4 == 0, K % 4 == 0. */
+int rv_thick_freq_fwd(const float* x, const float* w, const float* bias, float* z2, int B, int Tin, int pad, void* stream);
+long rv_thick_freq_bwd_workspace_bytes(int B, int Tin, int pad);
+int rv_thick_freq_bwd(const float* dz2, const float* z2, const float* x, float* dw, float* db, int B, int Tin, int pad, int accumulate,
+                      void* workspace, long workspace_bytes, void* stream);
+int rv_thick_tconv_fwd(const float* z2, const float* wj, const float* bias, float* z3, int B, int T, int N, void* stream);
+int rv_thick_linear_dz(const float* dy, const float* wt, const float* z3, float* dz3, long M, long K, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

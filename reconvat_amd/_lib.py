@@ -76,6 +76,11 @@ SIGNATURES = {
     'rv_maxpool_w2_dropout_fwd': (I, [P, P, P, L, I, I, F, U, P, P]),
     'rv_maxpool_w2_dropout_bwd': (I, [P, P, P, L, I, I, F, P]),
     'rv_dropout': (I, [P, P, P, P, L, F, U, P, P]),
+    'rv_thick_freq_fwd': (I, [P, P, P, P, I, I, I, P]),
+    'rv_thick_freq_bwd_workspace_bytes': (L, [I, I, I]),
+    'rv_thick_freq_bwd': (I, [P, P, P, P, P, I, I, I, I, P, L, P]),
+    'rv_thick_tconv_fwd': (I, [P, P, P, P, I, I, I, P]),
+    'rv_thick_linear_dz': (I, [P, P, P, P, L, L, I, P]),
 }
 
 _lib = None

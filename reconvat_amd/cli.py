@@ -1,5 +1,5 @@
 """Shared body of the drop-in training entry points (train_UNet_Onset_VAT.py / train_UNet_VAT.py /
-train_baseline_onset_frame_VAT.py).
+train_baseline_onset_frame_VAT.py / train_baseline_Thickstun.py).
 
 Keeps the reference CLI (`python train_UNet_Onset_VAT.py with key=value ...`, keys and defaults of
 train_UNet_Onset_VAT.py:28-78 / train_UNet_VAT.py:26-79) and loop semantics (:128-154): epochs of
@@ -20,7 +20,7 @@ from torch.utils.data import DataLoader
 
 from . import UNet_Onset, UNet, dp
 from .dataset import prepare_VAT_dataset
-from .train import FlatAdam, TrainStep, train_VAT_model, cycle
+from .train import FlatAdam, TrainStep, train_VAT_model, train_model, cycle
 
 ds_ksize, ds_stride = (2, 2), (2, 2)
 mode = 'imagewise'
@@ -85,6 +85,31 @@ def baseline_config(o):
     return c
 
 
+def thickstun_config(o):
+    """Config scope of train_baseline_Thickstun.py:25-78 (the VAT keys are set and never used there; kept so the reference's
+    command lines parse)."""
+    c = dict(
+        root='runs', onset_stack=True, device='cuda:0', log=True, w_size=31, spec='Mel', resume_iteration=None, train_on='String',
+        n_heads=4, position=True, iteration=10, VAT_start=0, alpha=1, VAT=True, XI=1e-6, eps=1.3, small=True, supersmall=True,
+        KL_Div=False, reconstruction=False, batch_size=1, train_batch_size=1, sequence_length=327680, epoches=20000,
+        step_size_up=100, max_lr=1e-4, learning_rate=1e-4, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.98,
+        leave_one_out=None, clip_gradient_norm=3, refresh=False,
+        graph=True, fused_optimizer=True, saving_freq=10, logging_freq=10, device_feed=True,
+    )
+    c.update(o)
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
+        if 'batch_size' not in o:
+            c['batch_size'] //= 2
+        if 'sequence_length' not in o:
+            c['sequence_length'] //= 2
+        print(f"Reducing batch size to {c['batch_size']} and sequence_length to {c['sequence_length']} to save memory")
+    if 'validation_length' not in o:
+        c['validation_length'] = c['sequence_length']
+    if 'logdir' not in o:
+        c['logdir'] = f"{c['root']}/baseline_ThickStun-lr={c['learning_rate']}" + datetime.now().strftime('%y%m%d-%H%M%S')
+    return c
+
+
 class ScalarLog:
     """TensorBoard SummaryWriter when available, else one JSON line per (tag, step)."""
 
@@ -134,6 +159,8 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  logging_freq=logging_freq, dtype='fp32', **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    if onset_script == 'thickstun':
+        VAT = False                                        # train_baseline_Thickstun.py sets the VAT keys and never uses them
     if not str(device).startswith('cuda') or not torch.cuda.is_available():
         raise SystemExit(f"device={device!r}: this build runs the training path on an MI355X only (hand-written HIP kernels, no CPU "
                          "fallback); use device=cuda:0.  The reference's CPU plumbing run maps to the same command with device=cuda:0.")
@@ -169,7 +196,11 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                    'validation': paths(val_set), 'full_validation': paths(full_validation)}, fh, indent=0)
 
     torch.manual_seed(0)                                   # identical initial weights on every rank
-    if onset_script == 'baseline':
+    if onset_script == 'thickstun':
+        from .thickstun import Thickstun
+        cls = Thickstun
+        model = cls()
+    elif onset_script == 'baseline':
         from . import onset_frames as onf
         from .constants import N_BINS, MAX_MIDI, MIN_MIDI
         cls = {'onset_frame': onf.OnsetsAndFrames_VAT_full, 'frame': onf.Frame_stack_VAT, 'onset': onf.Onset_stack_VAT}[model_name]
@@ -215,7 +246,10 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         if graph and fused_optimizer:
             # whole-step hipGraph replay on static buffers (same loop semantics as train_VAT_model)
             model.train()
-            li, ui = cycle(l_loader), (cycle(ul_loader) if use_vat else None)
+            # (train_model, the Thickstun script's loop: one pass over the WHOLE loader per epoch instead of `iteration` steps)
+            whole = onset_script == 'thickstun'
+            li, ui = (iter(l_loader) if whole else cycle(l_loader)), (cycle(ul_loader) if use_vat else None)
+            iteration = len(l_loader) if whole else iteration
             total = 0.0
             t_epoch = time.perf_counter()
             for _ in range(iteration):
@@ -231,6 +265,8 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
             losses = step_runner.losses
             if rank == 0:
                 print(f'Train Epoch: {ep}\tLoss: {total / iteration:.6f}\t({(time.perf_counter() - t_epoch) / iteration * 1e3:.1f} ms/step)')
+        elif onset_script == 'thickstun':
+            _, losses, optimizer = train_model(model, ep, l_loader, optimizer, scheduler, clip_gradient_norm)
         else:
             _, losses, optimizer = train_VAT_model(model, iteration, ep, l_loader, ul_loader if VAT else None, optimizer,
                                                    scheduler, clip_gradient_norm, alpha, VAT, VAT_start)

@@ -2116,3 +2116,178 @@ class DropoutFn(Function):
 
 def dropout(x, p, training):
     return DropoutFn.apply(x, p) if (training and p > 0.0) else x
+
+
+# --------------------------------------------------------------------------------------------
+# Thickstun baseline (csrc/thickstun.hip): window-sharing form of model/Thickstun_model.py
+# --------------------------------------------------------------------------------------------
+THICK_F = 51               # rows of CNN_freq's output: (229 - 128) / 2 + 1
+THICK_TAPS = 25
+THICK_LINEAR_SPLITK = 48   # fixed (not tuned per M): a frame's logits must not depend on how many frames share the launch (chunked evaluation)
+
+
+def _pack_plain(w, tag, args, numel):
+    """Plain [tap][k][n] re-indexed copy of a weight through the packed-weight cache (part of the PackPlan table)."""
+    key = (w.data_ptr(), 'thick', tag)
+    ver = (_EPOCH[0], w._version, tuple(w.shape))
+    hit = _pack_cache.get(key)
+    if hit is not None and hit[0] == ver:
+        return hit[1]
+    out = torch.empty(numel, device=w.device, dtype=torch.float32)
+    call('rv_pack_weights', ptr(w), ptr(out), *args, stream())
+    _pack_put(key, (ver, out, w, args))
+    return out
+
+
+def thick_wj(w):
+    """CNN_time.weight [N, C, 1, 25] -> wj [25][N][C] (tap-major: the forward kernel's and the input-gradient GEMMs' operand)."""
+    n, c, _, taps = w.shape
+    return _pack_plain(w, 'wj', (taps, n, c, c * taps, taps, 0, 0, 1), w.numel()).view(taps, n, c)
+
+
+def thick_feature_index(c, f, channels=4096, rows=THICK_F):
+    """(checkpoint feature index c*rows + f of linear.weight, z3 feature index f*channels + c) of channel c, frequency row f."""
+    return c * rows + f, f * channels + c
+
+
+def thick_wlt(w, channels):
+    """linear.weight [88, channels*51] in the checkpoint's c*51 + f feature order -> [51*channels, 88]: transposed, z3's f*channels + c order."""
+    n, k = w.shape
+    rows = k // channels
+    return _pack_plain(w, 'wlt', (rows, channels, n, rows, k, 0, 0, 1), w.numel()).view(k, n)
+
+
+def thick_wlt_grad_to_checkpoint(dwlt, channels):
+    """Gradient in thick_wlt's layout [51*channels, 88] -> linear.weight's [88, channels*51]."""
+    k, n = dwlt.shape
+    return dwlt.view(k // channels, channels, n).permute(2, 1, 0).reshape(n, k)
+
+
+class ThickFreqFn(Function):
+    """z2 = relu(CNN_freq) per frame: x [B, Tin, 229] time-major -> [B, 51, Tin + 2*pad, 128]; the 2*pad zero frames of the reference's
+    F.pad come out as relu(bias).  No gradient flows to x (the spectrogram is a leaf)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, pad):
+        need_gpu(x, w, b)
+        x = x.contiguous()
+        bb, tin, bins = x.shape
+        assert bins == 229 and tuple(w.shape) == (128, 1, 128, 1), (x.shape, w.shape)
+        z2 = torch.empty((bb, THICK_F, tin + 2 * pad, 128), device=x.device, dtype=torch.float32)
+        call('rv_thick_freq_fwd', ptr(x), ptr(w), ptr(b), ptr(z2), bb, tin, pad, stream())
+        ctx.pad = pad
+        ctx.save_for_backward(x, z2)
+        return z2
+
+    @staticmethod
+    def backward(ctx, dz2):
+        x, z2 = ctx.saved_tensors
+        dz2 = dz2.contiguous()
+        bb, tin, _ = x.shape
+        dw = torch.empty((128, 1, 128, 1), device=x.device, dtype=torch.float32)
+        db = torch.empty(128, device=x.device, dtype=torch.float32)
+        nbytes = _lib.load().rv_thick_freq_bwd_workspace_bytes(bb, tin, ctx.pad)
+        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
+        call('rv_thick_freq_bwd', ptr(dz2), ptr(z2), ptr(x), ptr(dw), ptr(db), bb, tin, ctx.pad, 0, ptr(ws), nbytes, stream())
+        return None, dw, db, None
+
+
+class ThickTconvFn(Function):
+    """z3 = relu(CNN_time) over the Hankel view of z2 [B, 51, T+24, 128] -> [B, T, 51, N].  Forward: rv_thick_tconv_fwd (A operand
+    stationary in LDS).  Backward on rv_gemm through strided views: the input gradient as 25 accumulating GEMMs per clip (one per tap,
+    the 51 frequency rows batched), the weight gradient as one accumulating GEMM per (clip, frequency row) with the bias gradient riding
+    along as the row sums -- plain read-modify-write in stream order, no atomics, so both are run-to-run reproducible.
+    The incoming dz3 is expected to carry z3's ReLU mask already (ThickLinearFn applies it in its epilogue)."""
+
+    @staticmethod
+    def forward(ctx, z2, w, b):
+        need_gpu(z2, w, b)
+        bb, rows, tp, c = z2.shape
+        n = w.shape[0]
+        t = tp - (THICK_TAPS - 1)
+        assert rows == THICK_F and c == 128 and tuple(w.shape[1:]) == (c, 1, THICK_TAPS) and t >= 1, (z2.shape, w.shape)
+        z3 = torch.empty((bb, t, rows, n), device=z2.device, dtype=torch.float32)
+        call('rv_thick_tconv_fwd', ptr(z2), ptr(thick_wj(w)), ptr(b), ptr(z3), bb, t, n, stream())
+        ctx.save_for_backward(z2, w)
+        return z3
+
+    @staticmethod
+    def backward(ctx, dz3):
+        z2, w = ctx.saved_tensors
+        dz3 = dz3.contiguous()
+        bb, rows, tp, c = z2.shape
+        n = w.shape[0]
+        t = tp - (THICK_TAPS - 1)
+        dz2 = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dz2 = thick_tconv_dgrad(dz3, thick_wj(w), bb, t)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dwflat, db = thick_tconv_wgrad(dz3, z2)
+            dw = dwflat.view(n, THICK_TAPS, c).permute(0, 2, 1).reshape(n, c, 1, THICK_TAPS)      # [n][j][c] -> the checkpoint's [n][c][1][j]
+        return dz2, dw, db
+
+
+def thick_tconv_dgrad(dz3, wj, bb, t):
+    """dz2[b,f,s,c] = sum_j sum_n dz3[b,s-j,f,n] * W[n,c,j] (without z2's ReLU mask: its consumer applies it on load)."""
+    taps, n, c = wj.shape
+    rows, tp = THICK_F, t + taps - 1
+    dz2 = torch.zeros((bb, rows, tp, c), device=dz3.device, dtype=torch.float32)
+    for b in range(bb):
+        a = dz3.as_strided((t, n), (rows * n, 1), dz3.storage_offset() + b * t * rows * n)
+        for j in range(taps):
+            out = dz2.as_strided((t, c), (c, 1), (b * rows * tp + j) * c)
+            gemm(a, wj[j], out, accumulate=True, splitk=1, batch=rows, bstrides=(n, 0, tp * c))
+    return dz2
+
+
+def thick_tconv_wgrad(dz3, z2):
+    """(dW [N, 25*128] in (tap, channel) order, dbias [N]):  dW[n, j*128+c] = sum_{b,f,t} dz3[b,t,f,n] * z2[b,f,t+j,c]."""
+    bb, t, rows, n = dz3.shape
+    tp, c = z2.shape[2], z2.shape[3]
+    k = (tp - t + 1) * c
+    dw = torch.zeros((n, k), device=dz3.device, dtype=torch.float32)
+    db = torch.zeros(n, device=dz3.device, dtype=torch.float32)
+    for b in range(bb):
+        for f in range(rows):
+            a = dz3.as_strided((n, t), (1, rows * n), dz3.storage_offset() + (b * t * rows + f) * n)
+            hankel = z2.as_strided((t, k), (c, 1), z2.storage_offset() + (b * rows + f) * tp * c)
+            gemm(a, hankel, dw, accumulate=True, splitk=1, a_rowsum=db)
+    return dw, db
+
+
+class ThickLinearFn(Function):
+    """p = sigmoid(z3 @ W^T) for z3 [M, K] >= 0 (the reference's torch.relu(torch.flatten(z3)) is the identity on it) and the checkpoint's
+    linear.weight [88, K] (c*51 + f feature order; read through thick_wlt).  Backward returns the gradient of z3's PRE-activation:
+    rv_thick_linear_dz applies z3's ReLU mask in its epilogue, so no separate pass over the 535 MB gradient exists."""
+
+    @staticmethod
+    def forward(ctx, z3, w, channels):
+        need_gpu(z3, w)
+        m, k = z3.shape
+        n = w.shape[0]
+        assert z3.is_contiguous() and tuple(w.shape) == (n, k)
+        wlt = thick_wlt(w, channels)
+        y = torch.empty((m, n), device=z3.device, dtype=torch.float32)
+        gemm(z3, wlt, y, None, 1, splitk=THICK_LINEAR_SPLITK)
+        ctx.channels = channels
+        ctx.save_for_backward(z3, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z3, w, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        m, k = z3.shape
+        n = w.shape[0]
+        wlt = thick_wlt(w, ctx.channels)
+        dz = torch.empty_like(dy)
+        call('rv_sigmoid_bwd', ptr(dy), n, None, 0, ptr(y), n, ptr(dz), n, m, n, stream())
+        dz3 = dw = None
+        if ctx.needs_input_grad[0]:
+            dz3 = torch.empty_like(z3)
+            call('rv_thick_linear_dz', ptr(dz), ptr(wlt), ptr(z3), ptr(dz3), m, k, n, stream())
+        if ctx.needs_input_grad[1]:
+            dwlt = torch.empty((k, n), device=z3.device, dtype=torch.float32)
+            gemm(z3.t(), dz, dwlt, splitk=1)
+            dw = thick_wlt_grad_to_checkpoint(dwlt, ctx.channels)
+        return dz3, dw, None

@@ -85,6 +85,39 @@ def train_VAT_model(model, iteration, ep, l_loader, ul_loader, optimizer, schedu
     return predictions, losses, optimizer
 
 
+def train_model(model, ep, loader, optimizer, scheduler, clip_gradient_norm):
+    """Drop-in for model/helper_functions.py:542-568 (same arguments, same return value): ONE pass over the whole loader per epoch,
+    run_on_batch(batch) -> zero_grad -> backward -> step -> scheduler.step -> clip, in that order.  Works with any torch
+    optimiser/scheduler pair, or with ``FlatAdam`` (pass ``scheduler=None``: StepLR is built in)."""
+    model.train()
+    total_loss = 0
+    batch_idx = 0
+    batch_size = loader.batch_size
+    total_batch = len(loader.dataset) if hasattr(loader, 'dataset') else len(loader) * batch_size
+    for batch in loader:
+        predictions, losses, _ = model.run_on_batch(batch)
+        loss = sum(losses.values())
+        total_loss += loss.item()
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        if scheduler is not None:
+            scheduler.step()
+        if clip_gradient_norm:
+            # the reference clips AFTER the step (no effect on the update); kept for .grad parity
+            if isinstance(optimizer, FlatAdam):
+                optimizer.clip_grad_norm_(clip_gradient_norm)
+            else:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip_gradient_norm)
+        batch_idx += 1
+        print(f'Train Epoch: {ep} [{batch_idx * batch_size}/{total_batch}'
+              f'({100. * batch_idx * batch_size / total_batch:.0f}%)]'
+              f'\tLoss: {loss.item():.6f}', end='\r')
+    print(' ' * 100, end='\r')
+    print(f'Train Epoch: {ep}\tLoss: {total_loss / len(loader):.6f}')
+    return predictions, losses, optimizer
+
+
 def eval_model(model, ep, loader, VAT_start=0, VAT=False):
     """Drop-in for model/helper_functions.py:667-687: eval-mode run_on_batch over a loader, every loss key collected."""
     from collections import defaultdict
