@@ -231,6 +231,18 @@ int rv_crop_segments(const short* audio, const unsigned char* label, const unsig
                      const long* label_begin, int B, long seq_len, int n_steps, int n_keys, float* out_audio, float* onset,
                      float* offset, float* frame, float* out_velocity, void* stream);
 
+/* ---- audio ingest: rational-ratio polyphase FIR resampling with the channel downmix fused in.
+ *   y[m] = sum_n x[n] h[m M - n L],  x[n] = mean over the C channels of input frame n (zero outside the signal), L/M = sr_out/sr_in
+ * x: [T_in, C] interleaved frames, in_dtype 0 = int16 (scale 2^-15), 1 = int32 (2^-31), 2 = float32; it is the slice
+ * [in_offset, in_offset + T_in) of the signal and must hold every sample of the signal that outputs [m_start, m_start + n_out)
+ * touch (frames outside the slice read as zero).  bank [L, Kp] float32, 16-byte aligned: bank[p][u] = h[p + (F - u) L], F = half / L,
+ * Kp = taps per phase rounded up to a multiple of 4 (reconvat_amd/resample.py::design_filter builds it); L * Kp must not exceed
+ * rv_resample_max_coeffs().  y: n_out samples, out_dtype 0 = float32, 1 = int16 (round-half-even of 32768 y, saturated); y[0] is
+ * output m_start.  Each output is summed in one fixed order, so cutting a signal into several calls does not change a bit. */
+long rv_resample_max_coeffs(void);
+int rv_resample(const void* x, int in_dtype, long T_in, int C, long in_offset, const float* bank, int L, int M, int F, int Kp, void* y,
+                int out_dtype, long m_start, long n_out, void* stream);
+
 /* ---- Onsets&Frames baseline pieces (model/onset_frame_VAT.py:321-415,603-635) -------------------------------------
  * Bidirectional one-layer nn.LSTM(batch_first=True) recurrence (the `sequence_model` of Onset_Stack / Combine_Stack,
  * model/onset_frame_VAT.py:614,370-381,401-410).  The caller computes the input projections of every step with rv_gemm:

@@ -70,6 +70,8 @@ SIGNATURES = {
     'rv_counter_add': (I, [P, L, P, P]),
     'rv_clip_scale': (I, [P, L, P, F, P]),
     'rv_crop_segments': (I, [P, P, P, P, P, I, L, I, I, P, P, P, P, P, P]),
+    'rv_resample_max_coeffs': (L, []),
+    'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
     'rv_lstm_flag_bytes': (L, [I]),
     'rv_lstm_fwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'rv_lstm_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),

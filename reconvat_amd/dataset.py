@@ -6,7 +6,8 @@ Layering (the device feed `reconvat_amd/feed.py::DeviceCorpus` consumes the same
   file rules  : `MAPS`, `MAESTRO`, `MusicNet`, `Guqin` name the (audio, tsv) pairs of a group -- tables below restate the
                 reference's selection rules (model/dataset.py:145-420); `CachedFolder` takes any folder of `.pt` caches.
   ingest      : `ingest_track` = the `.pt` cache contract of model/dataset.py:85-142: cache hit -> torch.load, else decode
-                the audio (wav natively, flac through `soundfile` when that package exists), paint the tsv notes into the
+                the audio (wav natively, flac through `soundfile` when that package exists; any rate / channel count / PCM width
+                is brought to 16 kHz mono int16 by reconvat_amd/resample.py, on the dataset's device), paint the tsv notes into the
                 roll (`paint_roll`, 3 = onset, 2 = sustain, 1 = offset) and write the cache.
   item rule   : `crop_item` (model/dataset.py:35-69): `step_begin = RandomState(seed).randint(T - L) // 512`, audio / 2^15,
                 masks `label == 3`, `== 1`, `> 1`, velocity / 128 -- bit-exact against the oracle / reference golden
@@ -32,13 +33,16 @@ _MASKS = (('onset', lambda roll: roll == 3), ('offset', lambda roll: roll == 1),
 # ------------------------------------------------------------------------------------------------------------------
 # ingest: audio + tsv -> cached track
 # ------------------------------------------------------------------------------------------------------------------
-def read_audio_int16(path):
-    """16-bit PCM samples of a mono 16 kHz file as int16 [T]."""
+def decode_audio(path):
+    """(sample rate, samples [T] or [T, C]) of an audio file as it is stored: int16 (16-bit PCM), int32 (24- and 32-bit PCM, left
+    justified as scipy.io.wavfile delivers them) or float32 (float wav)."""
     if path.endswith('.wav'):
         from scipy.io import wavfile
         sr, pcm = wavfile.read(path)
-        if pcm.dtype != np.int16:
-            raise ValueError(f'{path}: expected 16-bit PCM, got {pcm.dtype}')
+        if pcm.dtype == np.float64:
+            pcm = pcm.astype(np.float32)
+        if pcm.dtype not in (np.int16, np.int32, np.float32):
+            raise ValueError(f'{path}: expected 16-, 24- or 32-bit PCM or float samples, got {pcm.dtype}')
     else:
         try:
             import soundfile
@@ -48,11 +52,35 @@ def read_audio_int16(path):
                 'Convert the corpus to 16 kHz wav (read natively) or create the caches with Preprocessing.ipynb / the '
                 'reference (model/dataset.py:85-142).') from e
         pcm, sr = soundfile.read(path, dtype='int16')
-    if sr != SAMPLE_RATE:
-        raise ValueError(f'{path}: sample rate {sr}, expected {SAMPLE_RATE}')
-    if pcm.ndim != 1:
-        raise ValueError(f'{path}: expected mono audio, got shape {pcm.shape}')
-    return np.ascontiguousarray(pcm)
+    if pcm.ndim > 2 or pcm.shape[0] == 0:
+        raise ValueError(f'{path}: expected [T] or [T, C] samples, got shape {pcm.shape}')
+    return int(sr), np.ascontiguousarray(pcm)
+
+
+_RESAMPLERS = {}
+
+
+def to_model_rate(sr, pcm, device='cpu'):
+    """Samples of any rate / channel count / PCM width -> SAMPLE_RATE mono int16 [T'] (reconvat_amd/resample.py: polyphase FIR with
+    the downmix fused in).  A HIP `device` runs the kernel, anything else the float64 host path; the two agree to within 1 LSB.
+    16 kHz mono int16 input is returned as it is."""
+    if sr == SAMPLE_RATE and pcm.ndim == 1 and pcm.dtype == np.int16:
+        return pcm
+    from . import resample
+    device = torch.device(device)
+    if device.type != 'cuda':
+        return resample.resample_host(pcm, sr, SAMPLE_RATE, out_dtype=np.int16)
+    key = (sr, str(device))
+    if key not in _RESAMPLERS:
+        _RESAMPLERS[key] = resample.Resampler(sr, SAMPLE_RATE, device, out_dtype=torch.int16)
+    return _RESAMPLERS[key](torch.from_numpy(pcm)).cpu().numpy()
+
+
+def read_audio_int16(path, device='cpu'):
+    """The samples of an audio file as SAMPLE_RATE mono int16 [T]: a 16 kHz mono 16-bit file as stored, any other rate, channel
+    count or sample width (16 / 24 / 32-bit PCM, float) through `to_model_rate` on `device`."""
+    sr, pcm = decode_audio(path)
+    return np.ascontiguousarray(to_model_rate(sr, pcm, device))
 
 
 def paint_roll(notes, n_steps):
@@ -78,14 +106,19 @@ def paint_roll(notes, n_steps):
     return label, velocity
 
 
-def ingest_track(audio_path, tsv_path, refresh=False):
+def ingest_track(audio_path, tsv_path, refresh=False, device='cpu'):
+    """`device`: where a file that is not 16 kHz mono 16-bit is resampled (a HIP device: the kernel; else the host path).  Such a
+    track's cache also records `source_rate`; label times need no correction, the resampler has no delay."""
     cache = os.path.splitext(audio_path)[0] + '.pt' if audio_path.endswith(('.flac', '.wav')) else audio_path
     if os.path.exists(cache) and not refresh:
         return torch.load(cache)
-    pcm = read_audio_int16(audio_path)
+    sr, pcm = decode_audio(audio_path)
+    pcm = np.ascontiguousarray(to_model_rate(sr, pcm, device))
     n_steps = (len(pcm) - 1) // HOP_LENGTH + 1
     label, velocity = paint_roll(np.loadtxt(tsv_path, delimiter='\t', skiprows=1), n_steps)
     track = dict(path=audio_path, audio=torch.from_numpy(pcm), label=torch.from_numpy(label), velocity=torch.from_numpy(velocity))
+    if sr != SAMPLE_RATE:
+        track['source_rate'] = sr
     torch.save(track, cache)
     return track
 
@@ -139,7 +172,7 @@ class PianoRollAudioDataset(Dataset):
         raise NotImplementedError
 
     def load(self, audio_path, tsv_path):
-        return ingest_track(audio_path, tsv_path, self.refresh)
+        return ingest_track(audio_path, tsv_path, self.refresh, self.device)
 
 
 def _audio_files(pattern):

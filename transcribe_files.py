@@ -5,7 +5,8 @@
 
 ``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
 
-Inputs: 16 kHz mono 16-bit ``.wav`` files or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
+Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
+resampled to 16 kHz mono on the model's device) or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
 """
 import os
 import sys
@@ -22,19 +23,26 @@ from reconvat_amd.midi import save_midi
 from reconvat_amd.sacred_lite import parse_cli
 
 
-def load_audio(path):
+def load_audio(path, device='cpu'):
+    """float32 [T] at 16 kHz.  A 16 kHz 16-bit wav is read as before; any other PCM / float wav (rate, channel count, 16 / 24 / 32
+    bit) is resampled and downmixed on `device` (reconvat_amd/resample.py: the kernel on a HIP device, else the host path)."""
     if path.endswith('.pt'):
         return torch.load(path)['audio'].float().div(32768.0)
-    with wave.open(path, 'rb') as w:
-        assert w.getframerate() == SAMPLE_RATE and w.getsampwidth() == 2, f'{path}: need 16 kHz 16-bit PCM'
-        x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, w.getnchannels()).mean(axis=1)
-    return torch.from_numpy(x.astype(np.float32) / 32768.0)
+    try:
+        with wave.open(path, 'rb') as w:
+            if w.getframerate() == SAMPLE_RATE and w.getsampwidth() == 2:
+                x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16).reshape(-1, w.getnchannels()).mean(axis=1)
+                return torch.from_numpy(x.astype(np.float32) / 32768.0)
+    except wave.Error:                          # float and extensible-format wav: not for the `wave` module
+        pass
+    from reconvat_amd.dataset import read_audio_int16
+    return torch.from_numpy(read_audio_int16(path, device)).float().div(32768.0)
 
 
 def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT'):
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
-        audio = load_audio(path).to(device)
+        audio = load_audio(path, device).to(device)
         with torch.no_grad():
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
