@@ -243,6 +243,23 @@ long rv_resample_max_coeffs(void);
 int rv_resample(const void* x, int in_dtype, long T_in, int C, long in_offset, const float* bank, int L, int M, int F, int Kp, void* y,
                 int out_dtype, long m_start, long n_out, void* stream);
 
+/* ---- whole-song evaluation on the device: note decoding, the painted roll, the frame-metric counters.
+ * Rolls are [T, 88] row-major, 1 <= T <= 2^24.  rv_eval_workspace_bytes(T): device scratch either call needs (0 for a T out of range).
+ * rv_eval_decode: onsets / frames float32 (16-byte aligned, may alias), thresholds compared in float32 (x > threshold), rule 1 = rule1
+ *   (a note needs the frame roll on at its onset), 2 = rule2.  A note starts where the thresholded onset roll rises and ends at the
+ *   first frame where neither roll is on (T if none).  notes [max_notes, 3] int32 rows (t, pitch, end) ordered by (t, pitch); *count
+ *   (device int) = notes in the rolls; rows past max_notes are not written (88 * ceil(T / 2) rows always suffice).  painted [T, 88]
+ *   uint8 (4-byte aligned): 1 on [t, end) of every note.  Three launches on `stream`, no host synchronisation, deterministic.
+ * rv_eval_frame_counts: ref / est uint8 rolls (8-byte aligned, non-zero = on) -> out[14] int64 (device): for the plain set and then
+ *   for the chroma set the sums over frames of c, n_ref, n_est, min(n_ref, n_est) - c, max(0, n_ref - n_est), max(0, n_est - n_ref),
+ *   max(n_ref, n_est) - c; plain c = |ref & est|, chroma c = sum over the 12 pitch classes (21 + key) % 12 of min(ref_k, est_k).
+ *   Integer arithmetic only, partial sums added in a fixed order. */
+long rv_eval_workspace_bytes(long T);
+int rv_eval_decode(const float* onsets, const float* frames, long T, float onset_threshold, float frame_threshold, int rule, int* notes,
+                   long max_notes, int* count, unsigned char* painted, void* workspace, long workspace_bytes, void* stream);
+int rv_eval_frame_counts(const unsigned char* ref, const unsigned char* est, long T, long* out, void* workspace, long workspace_bytes,
+                         void* stream);
+
 /* ---- Onsets&Frames baseline pieces (model/onset_frame_VAT.py:321-415,603-635) -------------------------------------
  * Bidirectional one-layer nn.LSTM(batch_first=True) recurrence (the `sequence_model` of Onset_Stack / Combine_Stack,
  * model/onset_frame_VAT.py:614,370-381,401-410).  The caller computes the input projections of every step with rv_gemm:

@@ -72,6 +72,9 @@ SIGNATURES = {
     'rv_crop_segments': (I, [P, P, P, P, P, I, L, I, I, P, P, P, P, P, P]),
     'rv_resample_max_coeffs': (L, []),
     'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
+    'rv_eval_workspace_bytes': (L, [L]),
+    'rv_eval_decode': (I, [P, P, L, F, F, I, P, L, P, P, P, L, P]),
+    'rv_eval_frame_counts': (I, [P, P, L, P, P, L, P]),
     'rv_lstm_flag_bytes': (L, [I]),
     'rv_lstm_fwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'rv_lstm_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),

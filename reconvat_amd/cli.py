@@ -40,6 +40,7 @@ def base_config(o, onset_script):
         learning_rate_decay_rate=0.98, leave_one_out=None, clip_gradient_norm=3, refresh=False,
         # MI355X-side extras (not in the reference)
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
+        device_metrics=True,   # validation: note decoding, frame counters and AP on the device; False = the host metric code
         dtype='fp32',          # 'bf16': opt-in experiment -- bf16-operand backward convs of the final graphs (forward stays fp32)
     )
     c.update(o)
@@ -74,6 +75,7 @@ def baseline_config(o):
         sequence_length=327680, epoches=20000, learning_rate=5e-4, learning_rate_decay_steps=10000,
         learning_rate_decay_rate=0.98, leave_one_out=None, clip_gradient_norm=3, refresh=False, reconstruction=False,
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
+        device_metrics=True,
     )
     c.update(o)
     if c['model_name'] not in ('onset_frame', 'frame', 'onset'):
@@ -95,6 +97,7 @@ def thickstun_config(o):
         step_size_up=100, max_lr=1e-4, learning_rate=1e-4, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.98,
         leave_one_out=None, clip_gradient_norm=3, refresh=False,
         graph=True, fused_optimizer=True, saving_freq=10, logging_freq=10, device_feed=True,
+        device_metrics=True,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -129,7 +132,7 @@ class ScalarLog:
         self.f.flush()
 
 
-def log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT, VAT_start):
+def log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT, VAT_start, device_metrics=False):
     """The scalar half of tensorboard_log (model/helper_functions.py:120-141): `evaluate_wo_velocity(validation_dataset, model,
     reconstruction=reconstruction, VAT=False)` -- precision / recall / f1 of every non-chroma metric logged under its key -- then
     `eval_model(model, ep, supervised_loader, VAT_start, VAT)` -- the mean of every eval-mode loss key."""
@@ -138,7 +141,7 @@ def log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_s
     was_training = model.training
     model.eval()
     with torch.no_grad():
-        metrics = evaluate_wo_velocity(val_set, model, reconstruction=reconstruction, VAT=False)
+        metrics = evaluate_wo_velocity(val_set, model, reconstruction=reconstruction, VAT=False, device_metrics=device_metrics)
     for key, values in metrics.items():
         if key.startswith('metric/') and values:
             _, category, name = key.split('/')
@@ -156,7 +159,7 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  train_batch_size, learning_rate, learning_rate_decay_steps, learning_rate_decay_rate, alpha,
                  clip_gradient_norm, validation_length, refresh, device, epoches, logdir, log, iteration, VAT_start, VAT,
                  XI, eps, reconstruction, graph, fused_optimizer, saving_freq, device_feed=True, model_complexity=48, model_name='onset_frame', VAT_mode='all',
-                 logging_freq=logging_freq, dtype='fp32', **_unused):
+                 logging_freq=logging_freq, dtype='fp32', device_metrics=True, **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if onset_script == 'thickstun':
@@ -278,7 +281,8 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
             # every `logging_freq` epochs (and after the first) note / frame metrics on the validation segments and the eval-mode
             # loss terms over the labelled loader
             if ep % logging_freq == 0 or ep == 1:
-                log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT and ep >= VAT_start, VAT_start)
+                log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT and ep >= VAT_start, VAT_start,
+                               device_metrics=device_metrics)
             for key, value in losses.items():
                 writer.add_scalar(key, float(value), ep)
             if ep % saving_freq == 0:
@@ -296,7 +300,8 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         print('Training finished, now evaluating on the test split (full songs)')
         model.eval()
         with torch.no_grad():
-            metrics = evaluate_wo_velocity(full_validation, model, reconstruction=False, save_path=os.path.join(logdir, 'MIDI_results'))
+            metrics = evaluate_wo_velocity(full_validation, model, reconstruction=False, save_path=os.path.join(logdir, 'MIDI_results'),
+                                           device_metrics=device_metrics)
         for key, values in metrics.items():
             if key.startswith('metric/'):
                 _, category, name = key.split('/')

@@ -65,3 +65,44 @@ def notes_to_frames(pitches, intervals, shape):
     time = np.arange(roll.shape[0])
     freqs = [roll[t, :].nonzero()[0] for t in time]
     return time, freqs
+
+
+_RULES = {'rule1': 1, 'rule2': 2}
+DEVICE_TILE_FRAMES = 64                        # frames per workgroup of the device decoder (RV_EVAL_TILE in csrc/eval.hip)
+
+
+def _device_roll(x):
+    """float32 [T, 88] contiguous and 16-byte aligned, as rv_eval_decode loads it."""
+    x = x.detach().to(torch.float32).contiguous()
+    return x.clone() if x.data_ptr() % 16 else x
+
+
+def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_threshold=0.5, rule='rule1'):
+    """``extract_notes_wo_velocity`` on the device (csrc/eval.hip): the rolls stay in HBM, three launches decode them,
+    and the only read-back is the note count followed by that many (t, pitch, end) rows.  Returns (pitches, intervals, painted):
+    pitches / intervals are NumPy arrays equal to the host function's; painted is the uint8 [T, 88] roll of the notes -- what
+    ``notes_to_frames`` paints -- left on the device for ``evaluate.evaluate_frames_device``."""
+    from . import _lib
+    if rule not in _RULES:
+        raise NameError('Please enter the correct rule name')
+    _lib.need_gpu(onsets, frames)
+    on, fr = _device_roll(onsets), _device_roll(frames)
+    if on.dim() != 2 or on.shape[1] != 88 or on.shape != fr.shape or on.device != fr.device:
+        raise ValueError(f'expected two [T, 88] rolls on one device, got {tuple(on.shape)} and {tuple(fr.shape)}')
+    T, dev = on.shape[0], on.device
+    max_notes = 88 * ((T + 1) // 2)                    # a pitch cannot rise more often than every other frame
+    with torch.cuda.device(dev):
+        ws_bytes = _lib.load().rv_eval_workspace_bytes(T)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        notes = torch.empty((max(max_notes, 1), 3), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        painted = torch.empty((T, 88), dtype=torch.uint8, device=dev)
+        _lib.call('rv_eval_decode', on.data_ptr(), fr.data_ptr(), T, float(onset_threshold), float(frame_threshold), _RULES[rule],
+                  notes.data_ptr(), max_notes, count.data_ptr(), painted.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+        n = int(count.item())
+    if n > max_notes:
+        raise RuntimeError(f'rv_eval_decode reported {n} notes, more than the bound of {max_notes}')
+    if n == 0:
+        return np.array([]), np.array([]), painted
+    rows = notes[:n].cpu().numpy().astype(np.int64)
+    return rows[:, 1].copy(), np.ascontiguousarray(rows[:, [0, 2]]), painted

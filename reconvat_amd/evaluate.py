@@ -18,7 +18,7 @@ from scipy.sparse.csgraph import maximum_bipartite_matching
 from scipy.stats import hmean
 
 from .constants import HOP_LENGTH, SAMPLE_RATE, MIN_MIDI
-from .decoding import extract_notes_wo_velocity, notes_to_frames
+from .decoding import extract_notes_wo_velocity, extract_notes_wo_velocity_device, notes_to_frames
 from .midi import save_midi
 
 eps = sys.float_info.epsilon
@@ -113,14 +113,15 @@ def match_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_to
 
 
 def evaluate_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance=0.05, pitch_tolerance=50.0,
-                   offset_ratio=0.2, offset_min_tolerance=0.05, beta=1.0):
-    """(precision, recall, f-measure, average overlap ratio of the matched pairs)."""
+                   offset_ratio=0.2, offset_min_tolerance=0.05, beta=1.0, match=None):
+    """(precision, recall, f-measure, average overlap ratio of the matched pairs).  ``match``: the matcher, ``match_notes`` unless
+    given (``match_notes_sparse`` returns the same pairs without the dense matrices)."""
     ref_intervals = np.asarray(ref_intervals, dtype=np.float64).reshape(-1, 2)
     est_intervals = np.asarray(est_intervals, dtype=np.float64).reshape(-1, 2)
     if len(ref_pitches) == 0 or len(est_pitches) == 0:
         return 0.0, 0.0, 0.0, 0.0
-    m = match_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance, pitch_tolerance, offset_ratio,
-                    offset_min_tolerance)
+    m = (match or match_notes)(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance, pitch_tolerance, offset_ratio,
+                               offset_min_tolerance)
     p, r = len(m) / len(est_pitches), len(m) / len(ref_pitches)
     f = (1 + beta ** 2) * p * r / (beta ** 2 * p + r) if (p + r) > 0 else 0.0
     ratios = []
@@ -128,6 +129,116 @@ def evaluate_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset
         (rs, re_), (es, ee) = ref_intervals[i], est_intervals[j]
         ratios.append((min(re_, ee) - max(rs, es)) / (max(re_, ee) - min(rs, es)))
     return p, r, f, float(np.mean(ratios)) if ratios else 0.0
+
+
+# ---------------------------------------------------------------------------------------------
+# the same metrics without the host's per-frame lists and dense note matrices
+# ---------------------------------------------------------------------------------------------
+_FRAME_KEYS = ('Precision', 'Recall', 'Accuracy', 'Substitution Error', 'Miss Error', 'False Alarm Error', 'Total Error')
+
+
+def match_notes_sparse(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance=0.05, pitch_tolerance=50.0,
+                       offset_ratio=0.2, offset_min_tolerance=0.05):
+    """``match_notes`` without an N_ref x N_est matrix: same arguments, same pair list.
+
+    Only pairs whose onsets lie within the tolerance can hit, so the candidates of a reference note are the estimates in a window
+    of the onset-sorted list (the window is a millisecond wider than the tolerance: the dense route rounds the distance to 0.1 ms
+    before it compares).  On the frame grid that is the estimates at most one hop (0.032 s <= 0.05 s < 0.064 s) away.  The float64
+    onset, pitch and offset tests of ``match_notes`` are then applied to the candidates with the same expressions, and the hits go
+    into a CSR matrix with the ``indptr`` / ``indices`` that ``csr_matrix(hit)`` has (rows in order, columns ascending), so
+    ``maximum_bipartite_matching`` walks the same graph and returns the same matching, not just one of the same size."""
+    ref_intervals = np.asarray(ref_intervals, dtype=np.float64).reshape(-1, 2)
+    est_intervals = np.asarray(est_intervals, dtype=np.float64).reshape(-1, 2)
+    n_ref, n_est = len(ref_intervals), len(est_intervals)
+    if n_ref == 0 or n_est == 0:
+        return []
+    ref_pitches, est_pitches = np.asarray(ref_pitches), np.asarray(est_pitches)
+    order = np.argsort(est_intervals[:, 0], kind='stable')
+    sorted_on = est_intervals[order, 0]
+    window = onset_tolerance + 1e-3
+    lo = np.searchsorted(sorted_on, ref_intervals[:, 0] - window, side='left')
+    hi = np.searchsorted(sorted_on, ref_intervals[:, 0] + window, side='right')
+    per_ref = hi - lo
+    rows = np.repeat(np.arange(n_ref), per_ref)
+    first = np.cumsum(per_ref) - per_ref
+    cols = order[np.repeat(lo, per_ref) + (np.arange(per_ref.sum()) - np.repeat(first, per_ref))]
+    hit = np.around(np.abs(ref_intervals[rows, 0] - est_intervals[cols, 0]), N_DECIMALS) <= onset_tolerance
+    rows, cols = rows[hit], cols[hit]
+    hit = np.abs(1200.0 * (np.log2(ref_pitches)[rows] - np.log2(est_pitches)[cols])) <= pitch_tolerance
+    rows, cols = rows[hit], cols[hit]
+    if offset_ratio is not None:
+        offset_d = np.around(np.abs(ref_intervals[rows, 1] - est_intervals[cols, 1]), N_DECIMALS)
+        tol = offset_ratio * (ref_intervals[:, 1] - ref_intervals[:, 0])
+        tol[tol <= offset_min_tolerance] = offset_min_tolerance
+        hit = offset_d <= tol[rows]
+        rows, cols = rows[hit], cols[hit]
+    by_row_col = np.lexsort((cols, rows))
+    rows, cols = rows[by_row_col], cols[by_row_col]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_ref))]).astype(np.int32)
+    graph = csr_matrix((np.ones(len(cols), dtype=bool), cols.astype(np.int32), indptr), shape=(n_ref, n_est))
+    match = maximum_bipartite_matching(graph, perm_type='column')
+    return [(i, int(j)) for i, j in enumerate(match) if j >= 0]
+
+
+def _frame_metrics_from_counts(counts):
+    """The 14-key dict of ``evaluate_frames`` from its fourteen integer sums (plain seven, chroma seven): same float64 expressions,
+    same zero guards."""
+    out = {}
+    for pre, (tp, n_ref, n_est, sub, miss, fa, tot) in (('', counts[:7]), ('Chroma ', counts[7:])):
+        out[pre + 'Precision'] = tp / n_est if n_est else 0.0
+        out[pre + 'Recall'] = tp / n_ref if n_ref else 0.0
+        out[pre + 'Accuracy'] = tp / (n_est + n_ref - tp) if (n_est + n_ref - tp) else 0.0
+        out[pre + 'Substitution Error'] = sub / n_ref if n_ref else 0.0
+        out[pre + 'Miss Error'] = miss / n_ref if n_ref else 0.0
+        out[pre + 'False Alarm Error'] = fa / n_ref if n_ref else 0.0
+        out[pre + 'Total Error'] = tot / n_ref if n_ref else 0.0
+    return out
+
+
+def evaluate_frames_device(ref_roll, est_roll):
+    """``evaluate_frames`` of two uint8 [T, 88] rolls on the device (the painted rolls of ``extract_notes_wo_velocity_device``):
+    rv_eval_frame_counts sums the integer counters, the ratios are formed here in float64.  On the 88 piano keys a frame's match
+    count is the popcount of ref & est, and the chroma count the sum over the 12 pitch classes of min(ref_k, est_k) -- the values
+    the host's greedy matching within half a semitone arrives at -- so the result equals ``evaluate_frames`` value for value."""
+    from . import _lib
+    _lib.need_gpu(ref_roll, est_roll)
+    if ref_roll.dtype != torch.uint8 or est_roll.dtype != torch.uint8:
+        raise TypeError('evaluate_frames_device: uint8 rolls expected')
+    if ref_roll.dim() != 2 or ref_roll.shape[1] != 88 or ref_roll.shape != est_roll.shape or ref_roll.device != est_roll.device:
+        raise ValueError('evaluate_frames_device: reference and estimate must be [T, 88] rolls of one song on one device')
+    ref, est = ref_roll.contiguous(), est_roll.contiguous()
+    ref = ref.clone() if ref.data_ptr() % 8 else ref
+    est = est.clone() if est.data_ptr() % 8 else est
+    T, dev = ref.shape[0], ref.device
+    with torch.cuda.device(dev):
+        ws_bytes = _lib.load().rv_eval_workspace_bytes(T)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty(14, dtype=torch.int64, device=dev)
+        _lib.call('rv_eval_frame_counts', ref.data_ptr(), est.data_ptr(), T, out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+        counts = out.tolist()
+    return _frame_metrics_from_counts(counts)
+
+
+def average_precision_device(y_true, score):
+    """scikit-learn's ``average_precision_score`` (binary labels, positive = 1) with the sort and the cumulative sums on the
+    tensors' device: AP = sum_n (R_n - R_{n-1}) P_n over the DISTINCT score values in descending order, P_n and R_n the precision
+    and recall of "score >= that value".  The counts are exact integers; the ratios and their sum are float64."""
+    y = (y_true.reshape(-1) == 1)
+    s = score.reshape(-1).to(y.device)
+    if s.numel() != y.numel() or s.numel() == 0:
+        raise ValueError('average_precision_device: labels and scores must have the same non-zero number of elements')
+    s, idx = torch.sort(s, descending=True)
+    tps = torch.cumsum(y[idx].to(torch.int64), 0)
+    last = torch.ones_like(s, dtype=torch.bool)                         # last position of each run of equal scores
+    last[:-1] = s[1:] != s[:-1]
+    tps = tps[last].to(torch.float64)
+    seen = (torch.nonzero(last).reshape(-1) + 1).to(torch.float64)      # tps + fps
+    if float(tps[-1]) == 0.0:                                           # no positive label: sklearn's recall-is-one convention gives 0
+        return 0.0
+    precision = tps / seen
+    recall = tps / tps[-1]
+    step = recall - torch.cat([recall.new_zeros(1), recall[:-1]])
+    return float((step * precision).sum())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -146,11 +257,15 @@ def _frames_to_eval_units(t, freqs):
 
 
 def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, save_path=None, reconstruction=True,
-                         onset=True, pseudo_onset=False, rule='rule2', VAT=False):
+                         onset=True, pseudo_onset=False, rule='rule2', VAT=False, device_metrics=False):
     """model/evaluate_functions.py:20-127: whole-song evaluation; returns a dict of lists with the reference's keys
     (losses, metric/note/*, metric/note-with-offsets/*, metric/frame/*, metric/MusicNet/micro_avg_P, and the *_2
     variants of the reconstruction pass).  ``save_path``: per song `<basename>.pred.mid` (the transcription, reconvat_amd/midi.py)
-    and the `<basename>.label.png` / `.pred.png` piano rolls (model/utils.py:61-80), as the reference writes them (:119-126)."""
+    and the `<basename>.label.png` / `.pred.png` piano rolls (model/utils.py:61-80), as the reference writes them (:119-126).
+
+    ``device_metrics=True`` computes the same dictionary where the posteriorgrams are: notes and painted rolls by
+    ``extract_notes_wo_velocity_device``, frame metrics by ``evaluate_frames_device``, note matching by ``match_notes_sparse``, AP by
+    ``average_precision_device``; the per-frame lists of ``notes_to_frames`` are never built.  The model must be on a HIP device."""
     from sklearn.metrics import average_precision_score
     metrics = defaultdict(list)
     for label in data:
@@ -161,42 +276,54 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
             if pred.get(key) is not None:
                 pred[key] = pred[key].detach().squeeze(0).relu()
         lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
-        if onset:
-            p_ref, i_ref = extract_notes_wo_velocity(lab_on, lab_fr, rule=rule)
-            p_est, i_est = extract_notes_wo_velocity(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
-                                                     frame_threshold, rule=rule)
+        if device_metrics:
+            lab_on, lab_fr = lab_on.to(pred['frame'].device), lab_fr.to(pred['frame'].device)
+            decode = extract_notes_wo_velocity_device
         else:
-            p_ref, i_ref = extract_notes_wo_velocity(lab_fr, lab_fr, rule=rule)
-            p_est, i_est = extract_notes_wo_velocity(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule)
-        t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
-        t_est, f_est = _frames_to_eval_units(*notes_to_frames(p_est, i_est, pred['frame'].shape))
+            decode = extract_notes_wo_velocity
+        if onset:
+            p_ref, i_ref, *roll_ref = decode(lab_on, lab_fr, rule=rule)
+            p_est, i_est, *roll_est = decode(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
+                                             frame_threshold, rule=rule)
+        else:
+            p_ref, i_ref, *roll_ref = decode(lab_fr, lab_fr, rule=rule)
+            p_est, i_est, *roll_est = decode(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule)
+        if not device_metrics:
+            t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
+            t_est, f_est = _frames_to_eval_units(*notes_to_frames(p_est, i_est, pred['frame'].shape))
         p_ref, i_ref = _to_eval_units(p_ref, i_ref)
         p_est, i_est = _to_eval_units(p_est, i_est)
 
+        matcher = match_notes_sparse if device_metrics else match_notes
+
+        def average_precision(score):
+            if device_metrics:
+                return average_precision_device(lab_fr.flatten(), score.flatten())
+            return average_precision_score(lab_fr.cpu().flatten().numpy(), score.cpu().flatten().numpy())
+
         def note_block(suffix, pe, ie):
-            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe, offset_ratio=None)
+            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe, offset_ratio=None, match=matcher)
             for k, v in zip(('precision', 'recall', 'f1', 'overlap'), (p, r, f, o)):
                 metrics[f'metric/note/{k}{suffix}'].append(v)
-            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe)
+            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe, match=matcher)
             for k, v in zip(('precision', 'recall', 'f1', 'overlap'), (p, r, f, o)):
                 metrics[f'metric/note-with-offsets/{k}{suffix}'].append(v)
 
         note_block('', p_est, i_est)
-        frame_metrics = evaluate_frames(t_ref, f_ref, t_est, f_est)
+        frame_metrics = evaluate_frames_device(roll_ref[0], roll_est[0]) if device_metrics else evaluate_frames(t_ref, f_ref, t_est, f_est)
         metrics['metric/frame/f1'].append(hmean([frame_metrics['Precision'] + eps, frame_metrics['Recall'] + eps]) - eps)
-        metrics['metric/MusicNet/micro_avg_P'].append(
-            average_precision_score(lab_fr.cpu().flatten().numpy(), pred['frame'].cpu().flatten().numpy()))
+        metrics['metric/MusicNet/micro_avg_P'].append(average_precision(pred['frame']))
         if reconstruction and pred.get('frame2') is not None:
-            p2, i2 = extract_notes_wo_velocity(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold)
-            t2, f2 = _frames_to_eval_units(*notes_to_frames(p2, i2, pred['frame2'].shape))
+            p2, i2, *roll2 = decode(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold)
+            if not device_metrics:
+                t2, f2 = _frames_to_eval_units(*notes_to_frames(p2, i2, pred['frame2'].shape))
             p2, i2 = _to_eval_units(p2, i2)
             note_block('_2', p2, i2)
-            fm2 = evaluate_frames(t_ref, f_ref, t2, f2)
+            fm2 = evaluate_frames_device(roll_ref[0], roll2[0]) if device_metrics else evaluate_frames(t_ref, f_ref, t2, f2)
             frame_metrics['Precision_2'], frame_metrics['Recall_2'], frame_metrics['accuracy_2'] = \
                 fm2['Precision'], fm2['Recall'], fm2['Accuracy']
             metrics['metric/frame/f1_2'].append(hmean([fm2['Precision'] + eps, fm2['Recall'] + eps]) - eps)
-            metrics['metric/MusicNet/micro_avg_P2'].append(
-                average_precision_score(lab_fr.cpu().flatten().numpy(), pred['frame2'].cpu().flatten().numpy()))
+            metrics['metric/MusicNet/micro_avg_P2'].append(average_precision(pred['frame2']))
         for key, value in frame_metrics.items():
             metrics['metric/frame/' + key.lower().replace(' ', '_')].append(value)
         if save_path is not None:

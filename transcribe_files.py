@@ -17,7 +17,7 @@ import torch
 
 import reconvat_amd as ra
 from reconvat_amd.constants import HOP_LENGTH, SAMPLE_RATE, MIN_MIDI
-from reconvat_amd.decoding import extract_notes_wo_velocity
+from reconvat_amd.decoding import extract_notes_wo_velocity, extract_notes_wo_velocity_device
 from reconvat_amd.evaluate import midi_to_hz
 from reconvat_amd.midi import save_midi
 from reconvat_amd.sacred_lite import parse_cli
@@ -46,7 +46,10 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
         with torch.no_grad():
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
-        p_est, i_est = extract_notes_wo_velocity(onset, frame, onset_threshold, frame_threshold, rule=rule)
+        if frame.is_cuda:                       # decode where the posteriorgrams are (csrc/eval.hip); same notes as the host decoder
+            p_est, i_est, _ = extract_notes_wo_velocity_device(onset, frame, onset_threshold, frame_threshold, rule=rule)
+        else:
+            p_est, i_est = extract_notes_wo_velocity(onset, frame, onset_threshold, frame_threshold, rule=rule)
         scaling = HOP_LENGTH / SAMPLE_RATE
         i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
         p_est = np.array([midi_to_hz(MIN_MIDI + m) for m in p_est])
