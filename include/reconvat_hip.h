@@ -260,6 +260,22 @@ int rv_eval_decode(const float* onsets, const float* frames, long T, float onset
 int rv_eval_frame_counts(const unsigned char* ref, const unsigned char* est, long T, long* out, void* workspace, long workspace_bytes,
                          void* stream);
 
+/* ---- decoding thresholds swept over a grid: the integer counters behind note and frame precision / recall at every
+ * pair of n_on onset and n_fr frame thresholds (1..32 each, float32 on the device, any order, duplicates allowed), for one song.
+ * rv_eval_sweep_workspace_bytes: device scratch for the bit masks (0 for arguments out of range).
+ * onsets / frames as for rv_eval_decode (may alias).  ref_notes [n_ref, 5] int32 rows (t, pitch, end, early, late) SORTED BY
+ *   (pitch, t): the notes rv_eval_decode finds in the labels, plus the number of frames an estimate may end before (`early`) or
+ *   after (`late`) `end` and still pass the offset test -- the caller evaluates its float64 tolerance once per reference note, the
+ *   kernels stay all-integer.  n_ref may be 0.  ref_roll [T, 88] uint8 (4-byte aligned): the painted roll of those notes.
+ * counts [n_on][n_fr][5] int64 (device): estimated notes; reference notes matched one-to-one to an estimate of the same pitch that
+ *   starts within one frame (a maximum matching); the same with the offset test; frames painted by both; frames painted by the
+ *   estimate -- each what rv_eval_decode + the host matcher + rv_eval_frame_counts give at that pair.  ref_totals [2] int64: n_ref,
+ *   frames painted by the reference.  Two launches on `stream`, no host synchronisation, no atomics, deterministic. */
+long rv_eval_sweep_workspace_bytes(long T, int n_on, int n_fr);
+int rv_eval_sweep(const float* onsets, const float* frames, long T, const float* onset_thresholds, int n_on,
+                  const float* frame_thresholds, int n_fr, int rule, const int* ref_notes, long n_ref, const unsigned char* ref_roll,
+                  long* counts, long* ref_totals, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- Onsets&Frames baseline pieces (model/onset_frame_VAT.py:321-415,603-635) -------------------------------------
  * Bidirectional one-layer nn.LSTM(batch_first=True) recurrence (the `sequence_model` of Onset_Stack / Combine_Stack,
  * model/onset_frame_VAT.py:614,370-381,401-410).  The caller computes the input projections of every step with rv_gemm:

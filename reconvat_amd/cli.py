@@ -41,6 +41,7 @@ def base_config(o, onset_script):
         # MI355X-side extras (not in the reference)
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
         device_metrics=True,   # validation: note decoding, frame counters and AP on the device; False = the host metric code
+        tune_thresholds=False,  # True: choose onset / frame threshold on the validation set before the final evaluation
         dtype='fp32',          # 'bf16': opt-in experiment -- bf16-operand backward convs of the final graphs (forward stays fp32)
     )
     c.update(o)
@@ -75,7 +76,7 @@ def baseline_config(o):
         sequence_length=327680, epoches=20000, learning_rate=5e-4, learning_rate_decay_steps=10000,
         learning_rate_decay_rate=0.98, leave_one_out=None, clip_gradient_norm=3, refresh=False, reconstruction=False,
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
-        device_metrics=True,
+        device_metrics=True, tune_thresholds=False,
     )
     c.update(o)
     if c['model_name'] not in ('onset_frame', 'frame', 'onset'):
@@ -97,7 +98,7 @@ def thickstun_config(o):
         step_size_up=100, max_lr=1e-4, learning_rate=1e-4, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.98,
         leave_one_out=None, clip_gradient_norm=3, refresh=False,
         graph=True, fused_optimizer=True, saving_freq=10, logging_freq=10, device_feed=True,
-        device_metrics=True,
+        device_metrics=True, tune_thresholds=False,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -159,7 +160,7 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  train_batch_size, learning_rate, learning_rate_decay_steps, learning_rate_decay_rate, alpha,
                  clip_gradient_norm, validation_length, refresh, device, epoches, logdir, log, iteration, VAT_start, VAT,
                  XI, eps, reconstruction, graph, fused_optimizer, saving_freq, device_feed=True, model_complexity=48, model_name='onset_frame', VAT_mode='all',
-                 logging_freq=logging_freq, dtype='fp32', device_metrics=True, **_unused):
+                 logging_freq=logging_freq, dtype='fp32', device_metrics=True, tune_thresholds=False, **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if onset_script == 'thickstun':
@@ -299,16 +300,26 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         from .evaluate import evaluate_wo_velocity
         print('Training finished, now evaluating on the test split (full songs)')
         model.eval()
+        chosen = {}
+        if tune_thresholds:
+            # thresholds chosen on the validation split, the test songs then evaluated at the chosen pair
+            from .evaluate import tune_thresholds as sweep_validation
+            grid = [round(0.1 * k, 1) for k in range(1, 10)]
+            with torch.no_grad():
+                tuned = sweep_validation(val_set, model, grid, grid, device_metrics=device_metrics)
+            chosen = {'onset_threshold': tuned['onset_threshold'], 'frame_threshold': tuned['frame_threshold']}
+            print(f"Thresholds chosen on {tuned['songs']} validation items: onset {chosen['onset_threshold']:.2f}, frame "
+                  f"{chosen['frame_threshold']:.2f} (mean note F1 {tuned['best_value']:.4f})")
         with torch.no_grad():
             metrics = evaluate_wo_velocity(full_validation, model, reconstruction=False, save_path=os.path.join(logdir, 'MIDI_results'),
-                                           device_metrics=device_metrics)
+                                           device_metrics=device_metrics, **chosen)
         for key, values in metrics.items():
             if key.startswith('metric/'):
                 _, category, name = key.split('/')
                 print(f'{category:>32} {name:25}: {np.mean(values):.3f} \u00b1 {np.std(values):.3f}')
                 writer.add_scalar('validation/' + key, float(np.mean(values)), epoches)
         with open(os.path.join(logdir, 'result_dict'), 'wb') as fh:
-            pickle.dump(dict(metrics), fh)
+            pickle.dump(dict(metrics, **{'threshold/' + k.split('_')[0]: [v] for k, v in chosen.items()}), fh)
         f1 = float(np.mean(metrics['metric/frame/f1'])) if metrics['metric/frame/f1'] else float('nan')
         print(f'Training finished.  validation frame F1 {f1:.4f}, note F1 '
               f"{float(np.mean(metrics['metric/note/f1'])) if metrics['metric/note/f1'] else float('nan'):.4f}")

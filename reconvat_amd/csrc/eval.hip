@@ -25,6 +25,21 @@
 // Frame counters.  One work item per frame reads its two 88-byte rows, counts n_ref, n_est, c = |ref & est| and the chroma
 // c = sum over the 12 pitch classes of min(ref_k, est_k); workgroups write int64 partial sums of the fourteen counters and a
 // one-workgroup launch adds the partials in index order.  Integer arithmetic only; the host forms the ratios in float64.
+//
+// Threshold sweep.  The counters behind note and frame precision / recall at every pair of a grid of onset and frame
+// thresholds, two launches:
+//   1. sweep_masks_k  one workgroup per tile: both float tiles and the reference roll's tile go to LDS once; one work item per
+//                     (threshold, pitch) gathers its column into a 64-bit mask -- per onset threshold `on` and its rising edges
+//                     `rise`, per frame threshold `fr`, and once the reference roll -- so the rolls are read once for the whole grid.
+//   2. sweep_count_k  one workgroup per grid point, one work item per pitch.  A forward sweep over the tiles paints the estimate
+//                     (paint_runs with the painted state of the last frame as carry) and counts notes, painted frames and frames
+//                     painted on both sides.  Then the reference notes of the pitch (rows sorted by pitch, then time; the range of a
+//                     pitch is found by bisection) are walked in time order: a reference note starting at t can only hit an estimate
+//                     of the same pitch starting at t - 1, t or t + 1 (one hop <= 50 ms < two hops) and takes the earliest one that
+//                     is still free -- on a candidate graph that is a union of time-monotone paths this is a maximum matching.  The
+//                     offset test is integer: the host hands over, per reference note, how many frames the estimate may end early
+//                     or late, evaluated once with its own float64 expressions.
+// Integer work in a fixed order, no atomics: the counters are the same bits on every run.
 #include "common.h"
 
 #define RV_EVAL_KEYS 88
@@ -262,6 +277,154 @@ __global__ __launch_bounds__(64) void eval_frame_reduce_k(const long* __restrict
     }
 }
 
+// ---- threshold sweep ---------------------------------------------------------------------------------------------------------
+#define RV_SWEEP_MAX_THR 32
+#define RV_SWEEP_NOUT 5                        // per grid point: notes, matched, matched with offsets, frames on both sides, frames
+#define RV_SWEEP_REF_COLS 5                    // reference rows: t, pitch, end, frames the estimate may end early, ... or late
+
+struct SweepWs {                               // carved out of the caller's workspace; nt = tiles; every array [.][nt][88]
+    u64* on;                                   // [n_on]  onset roll > onset threshold
+    u64* rise;                                 // [n_on]  ... and not so the frame before
+    u64* fr;                                   // [n_fr]  frame roll > frame threshold
+    u64* ref;                                  // [1]     reference roll != 0
+};
+
+static long sweep_bytes(long nt, int n_on, int n_fr) { return (2L * n_on + n_fr + 1) * nt * RV_EVAL_KEYS * (long)sizeof(u64); }
+
+static SweepWs sweep_carve(void* workspace, long nt, int n_on, int n_fr) {
+    SweepWs w;
+    w.on = reinterpret_cast<u64*>(workspace);
+    w.rise = w.on + (long)n_on * nt * RV_EVAL_KEYS;
+    w.fr = w.rise + (long)n_on * nt * RV_EVAL_KEYS;
+    w.ref = w.fr + (long)n_fr * nt * RV_EVAL_KEYS;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void sweep_masks_k(const float* __restrict__ onsets, const float* __restrict__ frames,
+                                                     const unsigned char* __restrict__ ref_roll, long T, long nt,
+                                                     const float* __restrict__ thr_on, int n_on, const float* __restrict__ thr_fr,
+                                                     int n_fr, SweepWs w) {
+    __shared__ __attribute__((aligned(16))) float s_on[RV_EVAL_TILE * RV_EVAL_KEYS];
+    __shared__ __attribute__((aligned(16))) float s_fr[RV_EVAL_TILE * RV_EVAL_KEYS];
+    __shared__ __attribute__((aligned(16))) unsigned char s_ref[RV_EVAL_TILE * RV_EVAL_KEYS];
+    const long k = blockIdx.x, t0 = k * RV_EVAL_TILE;
+    const int rows = (int)(T - t0 < RV_EVAL_TILE ? T - t0 : RV_EVAL_TILE);
+    const int n = rows * RV_EVAL_KEYS;                                  // a multiple of 4: rows never split a 16-byte load
+    const float* o = onsets + t0 * RV_EVAL_KEYS;
+    const float* f = frames + t0 * RV_EVAL_KEYS;
+    const unsigned char* r = ref_roll + t0 * RV_EVAL_KEYS;
+    for (int i = threadIdx.x * 4; i < n; i += 256 * 4) {
+        *reinterpret_cast<f32x4*>(s_on + i) = *reinterpret_cast<const f32x4*>(o + i);
+        *reinterpret_cast<f32x4*>(s_fr + i) = *reinterpret_cast<const f32x4*>(f + i);
+        *reinterpret_cast<unsigned*>(s_ref + i) = *reinterpret_cast<const unsigned*>(r + i);
+    }
+    __syncthreads();
+    const int items = (n_on + n_fr + 1) * RV_EVAL_KEYS;
+    for (int item = threadIdx.x; item < items; item += 256) {
+        const int s = item / RV_EVAL_KEYS, p = item - s * RV_EVAL_KEYS;
+        u64 m = 0;
+        if (s < n_on + n_fr) {
+            const bool is_on = s < n_on;
+            const float thr = is_on ? thr_on[s] : thr_fr[s - n_on];
+            const float* col = (is_on ? s_on : s_fr) + p;
+            for (int t = 0; t < rows; ++t) m |= (u64)(col[t * RV_EVAL_KEYS] > thr ? 1u : 0u) << t;
+            if (is_on) {
+                const u64 prev = (t0 > 0 && onsets[(t0 - 1) * RV_EVAL_KEYS + p] > thr) ? 1ull : 0ull;
+                w.on[((long)s * nt + k) * RV_EVAL_KEYS + p] = m;
+                w.rise[((long)s * nt + k) * RV_EVAL_KEYS + p] = m & ~((m << 1) | prev);
+            } else {
+                w.fr[((long)(s - n_on) * nt + k) * RV_EVAL_KEYS + p] = m;
+            }
+        } else {
+            for (int t = 0; t < rows; ++t) m |= (u64)(s_ref[t * RV_EVAL_KEYS + p] != 0 ? 1u : 0u) << t;
+            w.ref[k * RV_EVAL_KEYS + p] = m;
+        }
+    }
+}
+
+// First index in [0, n) whose pitch column is >= pitch (n if none); rows sorted by pitch.  Terminates on any data.
+__device__ __forceinline__ long sweep_lower_bound(const int* __restrict__ rows, long n, int pitch) {
+    long lo = 0, hi = n;
+    while (lo < hi) {
+        const long mid = lo + ((hi - lo) >> 1);
+        if (rows[mid * RV_SWEEP_REF_COLS + 1] < pitch) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(128) void sweep_count_k(long T, long nt, int n_fr, int rule1, SweepWs w, const int* __restrict__ ref_notes,
+                                                     long n_ref, long* __restrict__ counts, long* __restrict__ ref_totals) {
+    __shared__ long red[RV_SWEEP_NOUT + 1][RV_EVAL_KEYS];
+    const int i = blockIdx.x / n_fr, j = blockIdx.x - i * n_fr, p = threadIdx.x;
+    if (p < RV_EVAL_KEYS) {
+        const u64* on = w.on + (long)i * nt * RV_EVAL_KEYS + p;
+        const u64* rise = w.rise + (long)i * nt * RV_EVAL_KEYS + p;
+        const u64* fr = w.fr + (long)j * nt * RV_EVAL_KEYS + p;
+        const u64* ref = w.ref + p;
+        const u64 keep = rule1 ? 0ull : ~0ull;                          // rule1: a start needs the frame roll on
+        long notes = 0, est_frames = 0, both = 0, ref_frames = 0;
+        u64 carry = 0;                                                  // painted state of the frame before the tile
+#pragma unroll 4
+        for (long k = 0; k < nt; ++k) {
+            const u64 f = fr[k * RV_EVAL_KEYS], a = on[k * RV_EVAL_KEYS] | f, s = rise[k * RV_EVAL_KEYS] & (f | keep);
+            const u64 r = ref[k * RV_EVAL_KEYS];
+            const u64 painted = paint_runs(s | (carry & a), a);
+            carry = painted >> 63;
+            notes += __popcll(s);
+            est_frames += __popcll(painted);
+            both += __popcll(painted & r);
+            ref_frames += __popcll(r);
+        }
+        long matched = 0, matched_off = 0;
+        long used = -1, used_off = -1;                                  // start frame of the last estimate taken (they only move on)
+        const long first = sweep_lower_bound(ref_notes, n_ref, p), last = sweep_lower_bound(ref_notes, n_ref, p + 1);
+        for (long q = first; q < last; ++q) {
+            const int* row = ref_notes + q * RV_SWEEP_REF_COLS;
+            const long t = row[0], end = row[2], early = row[3], late = row[4];
+            bool open = true, open_off = true;                          // this reference note is still unmatched
+            for (long c = t - 1; c <= t + 1; ++c) {
+                if (c < 0 || c >= T) continue;
+                const long k = c >> 6;
+                const int b = (int)(c & 63);
+                const u64 f = fr[k * RV_EVAL_KEYS];
+                if (!(((rise[k * RV_EVAL_KEYS] & (f | keep)) >> b) & 1ull)) continue;
+                if (open && c > used) {
+                    used = c;
+                    ++matched;
+                    open = false;
+                }
+                if (open_off && c > used_off) {
+                    u64 m = ~(on[k * RV_EVAL_KEYS] | f) & (~0ull << b);   // the estimate ends at the first inactive frame
+                    long kk = k;
+                    while (!m && ++kk < nt) m = ~(on[kk * RV_EVAL_KEYS] | fr[kk * RV_EVAL_KEYS]);
+                    long e = m ? kk * RV_EVAL_TILE + __builtin_ctzll(m) : T;
+                    if (e > T) e = T;
+                    const long d = e - end;
+                    if (d >= -early && d <= late) {
+                        used_off = c;
+                        ++matched_off;
+                        open_off = false;
+                    }
+                }
+            }
+        }
+        red[0][p] = notes;
+        red[1][p] = matched;
+        red[2][p] = matched_off;
+        red[3][p] = both;
+        red[4][p] = est_frames;
+        red[5][p] = ref_frames;
+    }
+    __syncthreads();
+    if (threadIdx.x <= RV_SWEEP_NOUT) {
+        long s = 0;
+        for (int q = 0; q < RV_EVAL_KEYS; ++q) s += red[threadIdx.x][q];
+        if (threadIdx.x < RV_SWEEP_NOUT) counts[(long)blockIdx.x * RV_SWEEP_NOUT + threadIdx.x] = s;
+        else if (blockIdx.x == 0) ref_totals[1] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 127) ref_totals[0] = n_ref;
+}
+
 extern "C" {
 
 // Bytes of device scratch that rv_eval_decode and rv_eval_frame_counts need for rolls of T frames (either call; 0 for a bad T).
@@ -314,6 +477,46 @@ int rv_eval_frame_counts(const unsigned char* ref, const unsigned char* est, lon
     hipLaunchKernelGGL(eval_frame_counts_k, dim3(nb), dim3(256), 0, st, ref, est, T, partial);
     hipLaunchKernelGGL(eval_frame_reduce_k, dim3(1), dim3(64), 0, st, (const long*)partial, nb, out);
     RV_LAUNCH_CHECK("rv_eval_frame_counts");
+    return RV_OK;
+}
+
+// Bytes of device scratch that rv_eval_sweep needs for rolls of T frames and an n_on x n_fr grid (0 for arguments out of range).
+long rv_eval_sweep_workspace_bytes(long T, int n_on, int n_fr) {
+    if (T < 1 || T > RV_EVAL_MAX_FRAMES || n_on < 1 || n_on > RV_SWEEP_MAX_THR || n_fr < 1 || n_fr > RV_SWEEP_MAX_THR) return 0;
+    return (sweep_bytes((T + RV_EVAL_TILE - 1) / RV_EVAL_TILE, n_on, n_fr) + 15) & ~15L;
+}
+
+// onsets, frames: [T, 88] float32 (16-byte aligned, may alias).  onset_thresholds [n_on], frame_thresholds [n_fr]: float32 on the
+// device, any order, duplicates allowed.  ref_notes: [n_ref, 5] int32 rows (t, pitch, end, early, late) sorted by (pitch, t) -- the
+// notes rv_eval_decode finds in the labels, and how many frames an estimate may end before / after `end` and still pass the offset
+// test; n_ref may be 0.  ref_roll: [T, 88] uint8 (4-byte aligned), the painted roll of those notes.  counts: [n_on][n_fr][5] int64
+// (notes, matched on onset and pitch, matched on onset, pitch and offset, frames painted on both sides, frames painted by the
+// estimate); ref_totals: 2 int64 (n_ref, frames painted by the reference).
+int rv_eval_sweep(const float* onsets, const float* frames, long T, const float* onset_thresholds, int n_on,
+                  const float* frame_thresholds, int n_fr, int rule, const int* ref_notes, long n_ref, const unsigned char* ref_roll,
+                  long* counts, long* ref_totals, void* workspace, long workspace_bytes, void* stream) {
+    RV_CHECK_ARG(onsets && frames && onset_thresholds && frame_thresholds && ref_roll && counts && ref_totals && workspace,
+                 "rv_eval_sweep: null pointer");
+    RV_CHECK_ARG(T >= 1 && T <= RV_EVAL_MAX_FRAMES, "rv_eval_sweep: T %ld not in 1..%ld", T, RV_EVAL_MAX_FRAMES);
+    RV_CHECK_ARG(n_on >= 1 && n_on <= RV_SWEEP_MAX_THR && n_fr >= 1 && n_fr <= RV_SWEEP_MAX_THR,
+                 "rv_eval_sweep: grid of %d x %d thresholds, 1..%d each", n_on, n_fr, RV_SWEEP_MAX_THR);
+    RV_CHECK_ARG(rule == 1 || rule == 2, "rv_eval_sweep: rule %d (1 = rule1, 2 = rule2)", rule);
+    RV_CHECK_ARG(n_ref >= 0 && n_ref <= RV_EVAL_KEYS * ((T + 1) / 2) && (n_ref == 0 || ref_notes),
+                 "rv_eval_sweep: %ld reference notes (at most 88 * ceil(T / 2), and a buffer for them)", n_ref);
+    RV_CHECK_ARG(((((uintptr_t)onsets) | ((uintptr_t)frames)) & 15) == 0 && (((uintptr_t)ref_roll) & 3) == 0 &&
+                     ((((uintptr_t)workspace) | ((uintptr_t)counts) | ((uintptr_t)ref_totals)) & 7) == 0 &&
+                     ((((uintptr_t)onset_thresholds) | ((uintptr_t)frame_thresholds) | ((uintptr_t)ref_notes)) & 3) == 0,
+                 "rv_eval_sweep: misaligned roll, list, output or workspace");
+    RV_CHECK_ARG(workspace_bytes >= rv_eval_sweep_workspace_bytes(T, n_on, n_fr), "rv_eval_sweep: workspace of %ld bytes, %ld needed",
+                 workspace_bytes, rv_eval_sweep_workspace_bytes(T, n_on, n_fr));
+    const long nt = (T + RV_EVAL_TILE - 1) / RV_EVAL_TILE;
+    const SweepWs w = sweep_carve(workspace, nt, n_on, n_fr);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sweep_masks_k, dim3((unsigned)nt), dim3(256), 0, st, onsets, frames, ref_roll, T, nt, onset_thresholds, n_on,
+                       frame_thresholds, n_fr, w);
+    hipLaunchKernelGGL(sweep_count_k, dim3(n_on * n_fr), dim3(128), 0, st, T, nt, n_fr, rule == 1 ? 1 : 0, w, ref_notes, n_ref, counts,
+                       ref_totals);
+    RV_LAUNCH_CHECK("rv_eval_sweep");
     return RV_OK;
 }
 

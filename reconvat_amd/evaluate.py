@@ -195,11 +195,9 @@ def _frame_metrics_from_counts(counts):
     return out
 
 
-def evaluate_frames_device(ref_roll, est_roll):
-    """``evaluate_frames`` of two uint8 [T, 88] rolls on the device (the painted rolls of ``extract_notes_wo_velocity_device``):
-    rv_eval_frame_counts sums the integer counters, the ratios are formed here in float64.  On the 88 piano keys a frame's match
-    count is the popcount of ref & est, and the chroma count the sum over the 12 pitch classes of min(ref_k, est_k) -- the values
-    the host's greedy matching within half a semitone arrives at -- so the result equals ``evaluate_frames`` value for value."""
+def frame_counts_device(ref_roll, est_roll):
+    """The fourteen integer sums behind ``evaluate_frames_device`` (rv_eval_frame_counts: plain tp, n_ref, n_est, substitutions, misses,
+    false alarms, total, then the chroma seven) of two uint8 [T, 88] rolls on the device, as a list of Python ints."""
     from . import _lib
     _lib.need_gpu(ref_roll, est_roll)
     if ref_roll.dtype != torch.uint8 or est_roll.dtype != torch.uint8:
@@ -215,8 +213,15 @@ def evaluate_frames_device(ref_roll, est_roll):
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         out = torch.empty(14, dtype=torch.int64, device=dev)
         _lib.call('rv_eval_frame_counts', ref.data_ptr(), est.data_ptr(), T, out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
-        counts = out.tolist()
-    return _frame_metrics_from_counts(counts)
+        return out.tolist()
+
+
+def evaluate_frames_device(ref_roll, est_roll):
+    """``evaluate_frames`` of two uint8 [T, 88] rolls on the device (the painted rolls of ``extract_notes_wo_velocity_device``):
+    rv_eval_frame_counts sums the integer counters, the ratios are formed here in float64.  On the 88 piano keys a frame's match
+    count is the popcount of ref & est, and the chroma count the sum over the 12 pitch classes of min(ref_k, est_k) -- the values
+    the host's greedy matching within half a semitone arrives at -- so the result equals ``evaluate_frames`` value for value."""
+    return _frame_metrics_from_counts(frame_counts_device(ref_roll, est_roll))
 
 
 def average_precision_device(y_true, score):
@@ -334,6 +339,196 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
             save_pianoroll(stem + '.pred.png', pred['onset'] if pred.get('onset') is not None else pred['frame'], pred['frame'])
             save_midi(stem + '.pred.mid', p_est, i_est, [127] * len(p_est))
     return metrics
+
+
+# ---------------------------------------------------------------------------------------------
+# decoding thresholds chosen on a validation set
+# ---------------------------------------------------------------------------------------------
+SWEEP_KEYS = ('n_est', 'matched', 'matched_with_offsets', 'frame_tp', 'frame_est')      # int64 [n_on, n_fr] each; order of rv_eval_sweep
+SWEEP_CRITERIA = ('note_f1', 'note_with_offsets_f1', 'frame_f1')
+MAX_SWEEP_THRESHOLDS = 32
+_SCALING = HOP_LENGTH / SAMPLE_RATE
+# the sweep kernel pairs a reference note with estimates that start at most one frame away: that IS the 50 ms onset tolerance of
+# match_notes on this frame grid (its rounded distances are 0.032 and 0.064)
+assert np.around(_SCALING, N_DECIMALS) <= 0.05 < np.around(2 * _SCALING, N_DECIMALS)
+
+
+def _sweep_grid(onset_thresholds, frame_thresholds):
+    on = np.atleast_1d(np.asarray(onset_thresholds, dtype=np.float32))
+    fr = np.atleast_1d(np.asarray(frame_thresholds, dtype=np.float32))
+    if on.ndim != 1 or fr.ndim != 1 or not 1 <= len(on) <= MAX_SWEEP_THRESHOLDS or not 1 <= len(fr) <= MAX_SWEEP_THRESHOLDS:
+        raise ValueError(f'threshold lists must hold 1..{MAX_SWEEP_THRESHOLDS} values each, got {on.shape} and {fr.shape}')
+    return on, fr
+
+
+def sweep_counts_host(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2'):
+    """The integer counters behind the note and frame metrics of one song at every pair of a threshold grid, by a plain loop over the
+    host functions: the labels are decoded once at 0.5 / 0.5, the posteriorgrams at every pair (``extract_notes_wo_velocity``,
+    float32 ``x > threshold``); ``match_notes`` without and with the offset test gives the two match counts, ``notes_to_frames`` the
+    painted frames.  Returns int64 [n_on, n_fr] arrays ``n_est``, ``matched``, ``matched_with_offsets``, ``frame_tp`` (frames painted by
+    reference and estimate), ``frame_est``, and the ints ``n_ref`` and ``frame_ref``.  The yardstick of ``sweep_counts_device``."""
+    on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
+    shape = tuple(frame_ref.shape)
+    p_ref, i_ref = extract_notes_wo_velocity(onset_ref, frame_ref, rule=rule)
+    _, f_ref = notes_to_frames(p_ref, i_ref, shape)
+    pr, ir = _to_eval_units(p_ref, i_ref)
+    out = {k: np.zeros((len(on_thr), len(fr_thr)), np.int64) for k in SWEEP_KEYS}
+    for a, t_on in enumerate(on_thr):
+        for b, t_fr in enumerate(fr_thr):
+            p_est, i_est = extract_notes_wo_velocity(onset_pred, frame_pred, float(t_on), float(t_fr), rule=rule)
+            _, f_est = notes_to_frames(p_est, i_est, shape)
+            pe, ie = _to_eval_units(p_est, i_est)
+            out['n_est'][a, b] = len(pe)
+            out['matched'][a, b] = len(match_notes(ir, pr, ie, pe, offset_ratio=None))
+            out['matched_with_offsets'][a, b] = len(match_notes(ir, pr, ie, pe))
+            out['frame_tp'][a, b] = sum(len(np.intersect1d(r, e)) for r, e in zip(f_ref, f_est))
+            out['frame_est'][a, b] = sum(len(e) for e in f_est)
+    out['n_ref'], out['frame_ref'] = len(pr), sum(len(r) for r in f_ref)
+    return out
+
+
+def _offset_slack(intervals):
+    """Per reference note (frame units [N, 2]) how many frames an estimate may end before / after the note's end and still pass
+    ``match_notes``' offset test -- that test evaluated here, once, with its own float64 expressions on times ``frame * 0.032``, so
+    the device compares integers.  The rounded distance grows with the frame difference, so the admissible differences are an
+    interval around 0; its two edges are looked for next to tolerance / hop."""
+    ref = np.asarray(intervals, dtype=np.int64).reshape(-1, 2)
+    times = (ref * _SCALING).reshape(-1, 2)
+    tol = 0.2 * (times[:, 1] - times[:, 0])
+    tol[tol <= 0.05] = 0.05
+    guess = np.floor(tol / _SCALING).astype(np.int64)
+    slack = []
+    for sign in (-1, 1):
+        best = np.zeros(len(ref), np.int64)
+        for step in range(-2, 3):
+            k = np.maximum(guess + step, 0)
+            ok = np.around(np.abs(times[:, 1] - (ref[:, 1] + sign * k) * _SCALING), N_DECIMALS) <= tol
+            best = np.where(ok, np.maximum(best, k), best)
+        slack.append(best)
+    return np.stack(slack, axis=1)
+
+
+def sweep_counts_device(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2'):
+    """``sweep_counts_host`` where the posteriorgrams are (csrc/eval.hip): same arguments, same result, two launches
+    for the whole grid.  The labels are decoded once by ``rv_eval_decode``; their notes go back to the device sorted by pitch with
+    the offset tolerance of each as a number of frames (``_offset_slack``), and ``rv_eval_sweep`` thresholds the rolls into bit masks
+    once per threshold and counts notes, matches and painted frames per pair.  Raises on a CPU tensor: no fallback."""
+    from . import _lib
+    from .decoding import _RULES, _device_roll
+    if rule not in _RULES:
+        raise NameError('Please enter the correct rule name')
+    on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
+    _lib.need_gpu(onset_ref, frame_ref, onset_pred, frame_pred)
+    p_ref, i_ref, roll_ref = extract_notes_wo_velocity_device(onset_ref, frame_ref, rule=rule)
+    on, fr = _device_roll(onset_pred), _device_roll(frame_pred)
+    if on.dim() != 2 or on.shape != fr.shape or on.shape != roll_ref.shape or not on.device == fr.device == roll_ref.device:
+        raise ValueError(f'expected [T, 88] rolls of one song on one device, got {tuple(on.shape)}, {tuple(fr.shape)} and labels '
+                         f'{tuple(roll_ref.shape)}')
+    T, dev, n_ref = on.shape[0], on.device, len(p_ref)
+    rows = np.zeros((max(n_ref, 1), 5), np.int32)
+    if n_ref:
+        order = np.lexsort((i_ref[:, 0], p_ref))
+        rows[:, 0], rows[:, 1], rows[:, 2] = i_ref[order, 0], p_ref[order], i_ref[order, 1]
+        rows[:, 3:] = np.minimum(_offset_slack(i_ref[order]), T)
+    n_on, n_fr = len(on_thr), len(fr_thr)
+    with torch.cuda.device(dev):
+        ws_bytes = _lib.load().rv_eval_sweep_workspace_bytes(T, n_on, n_fr)
+        if ws_bytes <= 0:
+            raise ValueError(f'rv_eval_sweep: no workspace for T = {T} and a {n_on} x {n_fr} grid')
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        thr = torch.from_numpy(np.concatenate([on_thr, fr_thr])).to(dev)
+        ref_notes = torch.from_numpy(rows).to(dev)
+        counts = torch.empty((n_on, n_fr, len(SWEEP_KEYS)), dtype=torch.int64, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.call('rv_eval_sweep', on.data_ptr(), fr.data_ptr(), T, thr.data_ptr(), n_on, thr.data_ptr() + 4 * n_on, n_fr, _RULES[rule],
+                  ref_notes.data_ptr(), n_ref, roll_ref.data_ptr(), counts.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes,
+                  _lib.stream())
+        counts, totals = counts.cpu().numpy(), totals.tolist()
+    out = {k: np.ascontiguousarray(counts[:, :, c]) for c, k in enumerate(SWEEP_KEYS)}
+    out['n_ref'], out['frame_ref'] = int(totals[0]), int(totals[1])
+    return out
+
+
+def sweep_metrics(counts, a, b):
+    """The nine metrics of one song at grid point (a, b) from its sweep counters, with the float64 expressions and zero guards of
+    ``evaluate_notes`` (beta = 1), ``evaluate_frames`` and the frame F1 of ``evaluate_wo_velocity``."""
+    n_ref, n_est, beta = int(counts['n_ref']), int(counts['n_est'][a, b]), 1.0
+    out = {}
+    for name, key in (('note', 'matched'), ('note_with_offsets', 'matched_with_offsets')):
+        m = int(counts[key][a, b])
+        if n_ref == 0 or n_est == 0:
+            p = r = f = 0.0
+        else:
+            p, r = m / n_est, m / n_ref
+            f = (1 + beta ** 2) * p * r / (beta ** 2 * p + r) if (p + r) > 0 else 0.0
+        out[name + '_precision'], out[name + '_recall'], out[name + '_f1'] = p, r, f
+    tp, fe, fr = int(counts['frame_tp'][a, b]), int(counts['frame_est'][a, b]), int(counts['frame_ref'])
+    out['frame_precision'] = tp / fe if fe else 0.0
+    out['frame_recall'] = tp / fr if fr else 0.0
+    out['frame_f1'] = hmean([out['frame_precision'] + eps, out['frame_recall'] + eps]) - eps
+    return out
+
+
+def best_threshold_index(values, onset_thresholds, frame_thresholds):
+    """Index (a, b) of the largest value; ties go to the pair nearest (0.5, 0.5) in max-norm (rounded to 1e-6), then to the lowest a,
+    then to the lowest b."""
+    values = np.asarray(values, dtype=np.float64)
+    far = np.round(np.maximum(np.abs(np.atleast_1d(np.asarray(onset_thresholds, np.float64)) - 0.5)[:, None],
+                              np.abs(np.atleast_1d(np.asarray(frame_thresholds, np.float64)) - 0.5)[None, :]), 6)
+    best = None
+    for a in range(values.shape[0]):
+        for b in range(values.shape[1]):
+            key = (-values[a, b], far[a, b], a, b)
+            if best is None or key < best:
+                best = key
+    return best[2], best[3]
+
+
+def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='note_f1', onset=True, pseudo_onset=False, rule='rule2',
+                    device_metrics=True, VAT=False):
+    """Choose ``onset_threshold`` / ``frame_threshold`` on a validation set.  One eval-mode ``run_on_batch`` per song of ``data`` (as
+    in ``evaluate_wo_velocity``; ``onset`` / ``pseudo_onset`` / ``rule`` / ``VAT`` mean what they mean there), then the sweep counters of
+    the song over the whole grid -- ``sweep_counts_device`` (``device_metrics=True``, model on a HIP device) or ``sweep_counts_host``
+    -- and from them per-song precision / recall / F1 of notes, notes with offsets and frames (``sweep_metrics``), averaged over the
+    songs with ``np.mean`` like the lists of ``evaluate_wo_velocity``: every grid value equals the mean of the matching
+    ``evaluate_wo_velocity`` list at that pair.
+
+    Returns ``{'onset_thresholds', 'frame_thresholds', 'grid': {metric: float64 [n_on, n_fr]}, 'criterion', 'best_index': (a, b),
+    'onset_threshold', 'frame_threshold', 'best_value', 'songs'}``.  The best pair maximises ``grid[criterion]`` (``note_f1``,
+    ``note_with_offsets_f1`` or ``frame_f1``).  Ties go to the pair nearest (0.5, 0.5) in max-norm (distances compared after rounding
+    to 1e-6, so that 0.3 and 0.7 are equally far), then to the lowest onset index, then to the lowest frame index."""
+    if criterion not in SWEEP_CRITERIA:
+        raise ValueError(f'criterion must be one of {SWEEP_CRITERIA}, got {criterion!r}')
+    on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
+    sweep = sweep_counts_device if device_metrics else sweep_counts_host
+    per_song = defaultdict(list)
+    for label in data:
+        pred, _, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
+        frame = pred['frame'].detach().squeeze(0).relu()
+        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
+        if device_metrics:
+            lab_on, lab_fr = lab_on.to(frame.device), lab_fr.to(frame.device)
+        if onset:
+            est_on = lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu()
+            counts = sweep(lab_on, lab_fr, est_on, frame, on_thr, fr_thr, rule=rule)
+        else:
+            counts = sweep(lab_fr, lab_fr, frame, frame, on_thr, fr_thr, rule=rule)
+        song = defaultdict(lambda: np.zeros((len(on_thr), len(fr_thr)), np.float64))
+        for a in range(len(on_thr)):
+            for b in range(len(fr_thr)):
+                for k, v in sweep_metrics(counts, a, b).items():
+                    song[k][a, b] = v
+        for k, v in song.items():
+            per_song[k].append(v)
+    if not per_song:
+        raise ValueError('tune_thresholds: no song in the validation set')
+    grid = {}
+    for k, v in per_song.items():                                       # np.mean of the per-song list, cell by cell: the scripts' average
+        grid[k] = np.array([[np.mean([song[a, b] for song in v]) for b in range(len(fr_thr))] for a in range(len(on_thr))])
+    a, b = best_threshold_index(grid[criterion], onset_thresholds, frame_thresholds)
+    return {'onset_thresholds': on_thr, 'frame_thresholds': fr_thr, 'grid': grid, 'criterion': criterion, 'best_index': (a, b),
+            'onset_threshold': float(on_thr[a]), 'frame_threshold': float(fr_thr[b]), 'best_value': float(grid[criterion][a, b]),
+            'songs': len(per_song[criterion])}
 
 
 def save_pianoroll(path, onsets, frames, onset_threshold=0.5, frame_threshold=0.5, zoom=4):

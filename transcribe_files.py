@@ -3,6 +3,8 @@
 
     python transcribe_files.py with device=cuda:0 weight=runs/.../model-final.pt input=Application/Input output=Application/Output
 
+``onset_threshold=`` / ``frame_threshold=`` (default 0.5 each) set the decoding thresholds -- tune_thresholds.py chooses a pair on
+the validation split.
 ``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
@@ -59,7 +61,8 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
 
 
 def main(argv):
-    cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel')
+    cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel', onset_threshold=0.5,
+               frame_threshold=0.5)
     cfg.update(parse_cli(argv))
     state = torch.load(cfg['weight'], map_location='cpu') if cfg['weight'] else None
     if state is not None:                       # the checkpoint's front-end buffers name its spectrogram
@@ -69,7 +72,8 @@ def main(argv):
         model.load_state_dict(state)
     model.to(cfg['device']).eval()
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
-    transcribe2midi(files, model, cfg['device'], cfg['output'])
+    transcribe2midi(files, model, cfg['device'], cfg['output'], onset_threshold=cfg['onset_threshold'],
+                    frame_threshold=cfg['frame_threshold'])
 
 
 if __name__ == '__main__':
