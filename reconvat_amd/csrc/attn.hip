@@ -10,7 +10,14 @@
 // fused [B*L, 3F] projection buffer); out, dout: [B, L, F] contiguous; relT: [31, F] (the parameter [F, 31]
 // transposed -- the host packs it once per optimiser step); att, de: [B, L, G, 31].
 //
-// One workgroup (5 waves) = (batch b, 16-frame tile, head g).  Both contractions run on v_mfma_f32_16x16x4_f32:
+// Two forms of every kernel, chosen per head shape by attn_form() (RV_ATTN_TILE=16 / 32 forces one; read when the library is loaded):
+//   the 32-frame form (attn_fwd32_k, attn_bwd_q32_k, attn_bwd_kv32_k; geometry and staging further down): one workgroup = (batch b,
+//   32-frame tile, head g), a 62-row window padded to 64, rows staged through buffer resources (out-of-range rows and pad columns arrive
+//   as zeros with no per-row test), each q/k/v row read 62/32 = 1.9 times;
+//   the 16-frame form (attn_fwd_k, attn_bwd_q_k, attn_bwd_kv_k, described next): the A/B baseline, and the form for views beyond the
+//   buffer-resource offset range.  Both produce the same bits (tests/test_attn_tiles_gpu.py).
+//
+// 16-frame form: one workgroup (5 waves) = (batch b, 16-frame tile, head g).  Both contractions run on v_mfma_f32_16x16x4_f32:
 //   scores  S[16 x 80] = X[16 x dh] . Y^T, Y = [ 46-row key window (padded to 48) ; rel^T (31 rows padded to 32) ]:
 //           one 16x16 tile per wave, operands read from LDS with ds_read_b128 (a lane's 4 floats feed 4 MFMAs);
 //           energy[t][w] = S[t][t+w] + S[t][48+w]
@@ -18,7 +25,7 @@
 //           for dq A = [ band(de) | de ] against [ key window ; rel^T ] (K = 80); output tiles round-robin over waves
 // The head dimension is padded to a multiple of 16 in LDS (229 -> 240, zero filled).  ~0.5 GFLOP per forward, so the
 // kernels are bound by staging the windows (each row is read 46/16 times, from L2).
-#include "common.h"
+#include "conv_shared.h"   // rv_make_rsrc / rv_buf_lds16 (the 32-frame form stages through buffer resources)
 #include <stdlib.h>
 #include <mutex>
 
@@ -51,6 +58,10 @@ struct AttnArgs {
     int seq_kv;                      // attn_bwd_kv_k: one window buffer used twice (see the kernel)
     int rel_regs;                    // attn_fwd_k / attn_bwd_q_k (wide heads): rel^T fragments straight from global memory into registers
                                      // instead of a 32-row LDS block, so that two workgroups fit a CU
+    // 32-frame form only: byte ranges of the buffer-resource views the windows are staged through (one (batch, head) column view each)
+    unsigned qkv_bytes, do_bytes, rel_bytes, co_bytes;   // q/k/v rows | dout rows | rel^T rows | att / de rows
+    int rel_first;                   // attn_bwd_q32_k: the rel^T terms of dq come before the window terms (the order the 16-frame form uses
+                                     // for this head shape: it follows ITS rel_regs choice, so both forms round alike)
 };
 
 // dst[r][f] (r < ntotal, f < dhp) = src[(row0 + r) * ld + col0 + f] for r < nvalid, 0 <= row0 + r < L, f < dh; else 0.
@@ -133,14 +144,16 @@ __device__ __forceinline__ f32x4 score_tile_regs(const float* X, const f32x4 (&y
 // O[t][f] = sum_k A[t][k] * Y[k][f] over NCH chunks of 16 k; wave `wave` owns the output tiles wave, wave+5, ...
 // Rows t0 + t of dst (row stride dld, first column col0) receive the result for f < dh.
 // rel^T rows as the B operand of apply_tiles, from global memory: yk[q][c][r] = relT[16 c + 4 g4 + r][col0 + 16 nt + i] (0 past row 30 / column dh)
-struct RelFrag { f32x4 y[AT_MAXT][2]; };
-__device__ __forceinline__ void rel_frag_load(RelFrag& rf, const float* relT, int F, int col0, int dh, int ntiles) {
+template <int MAXT> struct RelFragT { f32x4 y[MAXT][2]; };
+typedef RelFragT<AT_MAXT> RelFrag;
+template <int NW, int MAXT>
+__device__ __forceinline__ void rel_frag_load(RelFragT<MAXT>& rf, const float* relT, int F, int col0, int dh, int ntiles) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, g4 = lane >> 4;
 #pragma unroll
-    for (int q = 0; q < AT_MAXT; ++q) {
-        const int f = 16 * (wave + AT_NW * q) + i;
-        const bool fok = wave + AT_NW * q < ntiles && f < dh;
+    for (int q = 0; q < MAXT; ++q) {
+        const int f = 16 * (wave + NW * q) + i;
+        const bool fok = wave + NW * q < ntiles && f < dh;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -294,7 +307,7 @@ __global__ __launch_bounds__(AT_NTHR) void attn_bwd_q_k(AttnArgs a) {
     stage_rows(Ds, ldk, a.dout + (long)b * a.L * F, F, g * dh, dh, dhp, t0, AT_TT, AT_TT, a.L, a.dv4);
     stage_rows(Kx, ldk, a.v + boff, a.ld, g * dh, dh, dhp, t0 - AT_P, AT_WIN, AT_WINP, a.L, a.v4);
     RelFrag rf;
-    if (a.rel_regs) rel_frag_load(rf, a.rel, F, g * dh, dh, nchunk);      // (consumed by the last phase: the loads fly under everything else)
+    if (a.rel_regs) rel_frag_load<AT_NW>(rf, a.rel, F, g * dh, dh, nchunk);      // (consumed by the last phase: the loads fly under everything else)
     else stage_rows(Kx + AT_WINP * ldk, ldk, a.rel, F, g * dh, dh, dhp, 0, AT_W, 32, AT_W, a.dv4);
     for (int idx = tid; idx < AT_TT * AT_A3LD; idx += AT_NTHR) A3[idx] = 0.f;
     stage_wait();
@@ -380,6 +393,350 @@ __global__ __launch_bounds__(AT_NTHR) void attn_bwd_kv_k(AttnArgs a) {
     apply_tiles<3>(A5, AT_A2LD, Yq, ldk, nchunk, a.dk + orow, a.dld, g * dh, dh, a.L - s0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The 32-frame form: one workgroup = (batch b, 32-frame tile, head g); the window is 32 + 30 = 62 rows padded to 64, so a q/k/v row is
+// staged 62/32 = 1.9 times instead of 46/16 = 2.9 times and the per-workgroup fixed costs (rel^T, zeroing the banded matrix, barriers,
+// launch tail) are paid half as often.  Every number it produces is bit-identical to the 16-frame form's:
+//   scores  the two 16-row tiles need window column tiles {0,1,2} and {1,2,3} (the other two hold no band entry) plus two rel^T tiles
+//           each: 10 tiles of 16x16, each contracted over the head dimension in the same chunk order as score_tile always did
+//   apply   row tile rt multiplies window chunks rt .. rt+2 only -- the chunk in front of / behind its band holds exact zeros and is
+//           skipped, not multiplied -- i.e. exactly the three chunks, in the same order, of the 16-frame workgroup at t0 + 16 rt; the
+//           two row tiles share the B fragments of chunks 1 and 2
+// NW waves (5: two score tiles per wave; 10: one), output column tiles round-robin over the waves as before.
+#define AT2_TT 32
+#define AT2_WIN (AT2_TT + 2 * AT_P)  // 62 rows
+#define AT2_WINP 64                  // ... padded to four MFMA tiles
+#define AT2_SLD 96                   // raw score row: 64 window columns + 32 rel columns
+#define AT2_A2LD 68                  // banded matrix row (64 + pad)
+#define AT2_A3LD 100                 // [band | dense] row (96 + pad)
+#define AT2_NSCORE 10                // score tiles of the forward kernel: 6 window tiles, then 4 rel^T tiles
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void rv_buf_lds4(rv_rsrc_t rs, void* lds, unsigned voff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 4, voff, 0, 0, 0);
+}
+#else
+__device__ inline void rv_buf_lds4(rv_rsrc_t, void*, unsigned) {}
+#endif
+
+// stage_rows through a buffer resource over `bytes` bytes from `base` (the (batch, head) column view: row t at byte t * ld * 4, so
+// bytes = ((L - 1) * ld + dh) * 4).  An offset outside [0, bytes) makes the DMA write ZEROS (tools/probes/buffer_lds_oob.hip): rows in
+// front of / behind the sequence (negative offsets wrap to >= 0xC0000000), the tail rows r >= nvalid and the pad columns dh .. dhp
+// all arrive as zeros with no range test, no source select and no store.  Per lane one offset per slot is hoisted; per row the code is
+// one add and the DMA.  The host keeps (L + 64) * ld * 4 below 0x3f000000, so no sum below wraps into the view:
+//   kColOut (a pad column) + row bytes stays in [0x41000000, 0xbf000400], kRowOut (a tail row) + column bytes in [0x40000000, 0xc0000000].
+// v4: 16 bytes per lane (dhp <= 256: ONE instruction per row; the source needs 4-byte alignment only, tools/probes/glds16_unaligned.hip and
+// buffer_lds16_unaligned.hip) plus one 4-byte instruction of four lanes for a row tail of dh % 4 floats and the zeros behind it.
+template <int NW>
+__device__ __forceinline__ void stage_rows_buf(float* dst, int ldk, const float* base, unsigned bytes, int ld, int dh, int dhp, int row0,
+                                               int nvalid, int ntotal, bool v4) {
+    const rv_rsrc_t rs = rv_make_rsrc(base, bytes);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const unsigned kColOut = 0x80000000u, kRowOut = 0x40000000u;
+    float* drow = dst + wave * ldk;
+    int rb = (row0 + wave) * ld * 4;                                 // byte offset of this wave's next row (negative in front of the sequence)
+    const int rstep = NW * ld * 4, dstep = NW * ldk;
+    if (v4) {
+        const int nfull = dh & ~3, rem = dh - nfull, zlo = nfull + (rem ? 4 : 0), lf = 4 * lane;
+        const bool act = lf < nfull || (lf >= zlo && lf < dhp);      // whole quads of the row | whole quads of padding
+        const unsigned vo = lf < nfull ? lf * 4u : kColOut;
+        const unsigned vt = lane < rem ? (nfull + lane) * 4u : kColOut;
+        for (int r = wave; r < ntotal; r += NW, rb += rstep, drow += dstep) {
+            const unsigned ro = r < nvalid ? (unsigned)rb : kRowOut;
+            if (act) rv_buf_lds16(rs, drow, vo + ro);
+            if (rem && lane < 4) rv_buf_lds4(rs, drow + nfull, vt + ro);
+        }
+    } else {
+        for (int r = wave; r < ntotal; r += NW, rb += rstep, drow += dstep) {
+            const unsigned ro = r < nvalid ? (unsigned)rb : kRowOut;
+            for (int k = 0; k * 64 < dhp; ++k) {
+                const int f = k * 64 + lane;
+                if (f < dhp) rv_buf_lds4(rs, drow + k * 64, (f < dh ? f * 4u : kColOut) + ro);
+            }
+        }
+    }
+}
+
+// window score tile `id` (0..5) of a 32-frame workgroup: row tile rt against window column tile ct
+__device__ __forceinline__ void win_tile32(int id, int& rt, int& ct) { rt = id >= 3; ct = id - 2 * rt; }
+
+// O[32 x dh] = A[32 x 64] . Y[64 x dh] with A banded (see above: row tile rt takes chunks rt .. rt+2); REL: A carries 32 dense columns
+// behind the band (column 64 on) that multiply rel^T -- from LDS (Yrel) or, with `rf`, from register fragments -- in front of the window
+// terms (rel_first) or behind them.  Wave `wave` owns the output column tiles wave, wave + NW, ...
+template <int NW, bool REL>
+__device__ __forceinline__ void apply32(const float* A, int lda, const float* Y, int ldk, int ntiles, float* dst, long dld, int col0, int dh,
+                                        int nrows_valid, const float* Yrel = nullptr, const RelFragT<(16 + NW - 1) / NW>* rf = nullptr,
+                                        bool rel_first = false) {
+    constexpr int MAXT = (16 + NW - 1) / NW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, g4 = lane >> 4;
+    f32x4 acc[2][MAXT];
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q) acc[0][q] = acc[1][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto rel_part = [&]() {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(A + i * lda + AT2_WINP + 16 * c + 4 * g4);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(A + (16 + i) * lda + AT2_WINP + 16 * c + 4 * g4);
+#pragma unroll
+            for (int q = 0; q < MAXT; ++q) {
+                const int nt = wave + NW * q;
+                if (nt < ntiles) {
+                    f32x4 y;
+                    if (rf) y = rf->y[q][c];
+                    else {
+                        const float* yk = Yrel + (16 * c + 4 * g4) * ldk + 16 * nt + i;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) y[r] = yk[r * ldk];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[r], y[r], acc[0][q], 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[r], y[r], acc[1][q], 0, 0, 0);
+                }
+            }
+        }
+    };
+    if (REL && rel_first) rel_part();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        f32x4 a0 = (f32x4){0.f, 0.f, 0.f, 0.f}, a1 = a0;
+        if (c < 3) a0 = *reinterpret_cast<const f32x4*>(A + i * lda + 16 * c + 4 * g4);
+        if (c > 0) a1 = *reinterpret_cast<const f32x4*>(A + (16 + i) * lda + 16 * c + 4 * g4);
+        const float* yk = Y + (16 * c + 4 * g4) * ldk + i;
+#pragma unroll
+        for (int q = 0; q < MAXT; ++q) {
+            const int nt = wave + NW * q;
+            if (nt < ntiles) {
+                f32x4 y;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = yk[r * ldk + 16 * nt];
+                if (c < 3) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[r], y[r], acc[0][q], 0, 0, 0);
+                }
+                if (c > 0) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[r], y[r], acc[1][q], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (REL && !rel_first) rel_part();
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q) {
+        const int nt = wave + NW * q;
+        const int f = 16 * nt + i;
+        if (nt >= ntiles || f >= dh) continue;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t = 16 * rt + 4 * g4 + r;
+                if (t < nrows_valid) dst[(long)t * dld + col0 + f] = acc[rt][q][r];
+            }
+    }
+}
+
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void attn_fwd32_k(AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    static_assert(AT2_NSCORE % NW == 0, "the score tiles divide over the waves");
+    constexpr int NTHR = NW * 64, TPW = AT2_NSCORE / NW;
+    const int dh = a.dh, dhp = a.dhp, ldk = dhp + 4, nchunk = dhp >> 4, F = a.G * dh;
+    float* Qs = smem;                           // [32][ldk]
+    float* Kx = Qs + AT2_TT * ldk;              // [64][ldk]  key window, value window later
+    float* Rx = Kx + AT2_WINP * ldk;            // [32][ldk]  rel^T (absent with rel_regs)
+    float* Sr = Rx + (a.rel_regs ? 0 : 32) * ldk;   // [32][96]
+    float* A2 = Sr + AT2_TT * AT2_SLD;          // [32][68]
+    const int ntile = (a.L + AT2_TT - 1) / AT2_TT;
+    const int bx = xcd_remap(blockIdx.x, gridDim.x);     // an XCD (one L2) owns a run of neighbouring tiles: window overlap hits
+    const int b = bx / ntile, t0 = (bx - b * ntile) * AT2_TT;
+    const int g = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g4 = lane >> 4;
+    const long boff = (long)b * a.L * a.ld + g * dh;
+    const int id0 = wave * TPW;                 // this wave's score tiles: id0 .. id0 + TPW - 1 (0..5 window tiles, 6..9 rel^T tile (id - 6) >> 1 of row tile (id - 6) & 1)
+    if (RV_ATTN_ABL & 16) return;
+    if (!(RV_ATTN_ABL & 1)) {
+        stage_rows_buf<NW>(Qs, ldk, a.q + boff, a.qkv_bytes, (int)a.ld, dh, dhp, t0, AT2_TT, AT2_TT, a.v4);
+        stage_rows_buf<NW>(Kx, ldk, a.k + boff, a.qkv_bytes, (int)a.ld, dh, dhp, t0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+    }
+    f32x4 yb[16];                               // rel_regs: the waves of the rel^T tiles hold their score operand (row 16 c + i) in registers
+    if (a.rel_regs) {
+        if (id0 >= 6) {
+            const int w = 16 * ((id0 - 6) >> 1) + i;
+            const float* rp = a.rel + (long)min(w, AT_W - 1) * F + g * dh + 4 * g4;
+#pragma unroll
+            for (int c = 0; c < 16; ++c)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) yb[c][r] = (c < nchunk && w < AT_W && 16 * c + 4 * g4 + r < dh) ? rp[16 * c + r] : 0.f;
+        }
+    } else if (!(RV_ATTN_ABL & 1)) {
+        stage_rows_buf<NW>(Rx, ldk, a.rel + g * dh, a.rel_bytes, F, dh, dhp, 0, AT_W, 32, a.dv4);
+    }
+    for (int idx = tid; idx < AT2_TT * AT2_A2LD; idx += NTHR) A2[idx] = 0.f;
+    stage_wait();
+    __syncthreads();
+    if (!(RV_ATTN_ABL & 2)) {
+#pragma unroll
+        for (int j = 0; j < TPW; ++j) {
+            const int id = id0 + j;
+            int rt, col;
+            f32x4 s;
+            if (id < 6) {
+                int ct;
+                win_tile32(id, rt, ct);
+                s = score_tile(Qs + 16 * rt * ldk, Kx + 16 * ct * ldk, ldk, nchunk, i, g4);
+                col = 16 * ct;
+            } else {
+                rt = (id - 6) & 1;
+                const int c = (id - 6) >> 1;
+                s = a.rel_regs ? score_tile_regs(Qs + 16 * rt * ldk, yb, ldk, nchunk, i, g4)
+                               : score_tile(Qs + 16 * rt * ldk, Rx + 16 * c * ldk, ldk, nchunk, i, g4);
+                col = AT2_WINP + 16 * c;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Sr[(16 * rt + 4 * g4 + r) * AT2_SLD + col + i] = s[r];
+        }
+    }
+    __syncthreads();                            // scores complete, key window dead
+    if (!(RV_ATTN_ABL & 1)) stage_rows_buf<NW>(Kx, ldk, a.v + boff, a.qkv_bytes, (int)a.ld, dh, dhp, t0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+    if (!(RV_ATTN_ABL & 4)) {                   // softmax: 16 lanes per frame, two window slots per lane (the 16-frame form's arithmetic)
+        for (int t = tid >> 4; t < AT2_TT; t += NTHR / 16) {
+            const int l = tid & 15;
+            const float* sr = Sr + t * AT2_SLD;
+            const float e0 = sr[t + l] + sr[AT2_WINP + l];
+            const float e1 = l < 15 ? sr[t + l + 16] + sr[AT2_WINP + l + 16] : -INFINITY;
+            const float m = grp16_max(fmaxf(e0, e1));
+            float p0 = expf(e0 - m), p1 = l < 15 ? expf(e1 - m) : 0.f;
+            const float inv = 1.f / grp16_sum(p0 + p1);
+            p0 *= inv; p1 *= inv;
+            A2[t * AT2_A2LD + t + l] = p0;
+            if (l < 15) A2[t * AT2_A2LD + t + l + 16] = p1;
+            if (a.att && t0 + t < a.L) {
+                float* ar = a.att + (((long)b * a.L + t0 + t) * a.G + g) * AT_W;
+                ar[l] = p0;
+                if (l < 15) ar[l + 16] = p1;
+            }
+        }
+    }
+    stage_wait();
+    __syncthreads();
+    if (!(RV_ATTN_ABL & 8)) apply32<NW, false>(A2, AT2_A2LD, Kx, ldk, nchunk, a.out + ((long)b * a.L + t0) * F, F, g * dh, dh, a.L - t0);
+}
+
+// backward, query side: de (softmax backward) and dq for a 32-frame tile
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void attn_bwd_q32_k(AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NTHR = NW * 64, TPW = AT2_NSCORE / NW, MAXT = (16 + NW - 1) / NW;
+    const int dh = a.dh, dhp = a.dhp, ldk = dhp + 4, nchunk = dhp >> 4, F = a.G * dh;
+    float* Ds = smem;                           // [32][ldk]  dout tile
+    float* Kx = Ds + AT2_TT * ldk;              // [64][ldk]  value window, then key window
+    float* Rx = Kx + AT2_WINP * ldk;            // [32][ldk]  rel^T (absent with rel_regs)
+    float* Sr = Rx + (a.rel_regs ? 0 : 32) * ldk;   // [32][96]   dout . v^T (64 columns used)
+    float* A3 = Sr + AT2_TT * AT2_SLD;          // [32][100]  [ band(de) | de ]
+    const int ntile = (a.L + AT2_TT - 1) / AT2_TT;
+    const int bx = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = bx / ntile, t0 = (bx - b * ntile) * AT2_TT;
+    const int g = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = lane & 15, g4 = lane >> 4;
+    const long boff = (long)b * a.L * a.ld + g * dh;
+    stage_rows_buf<NW>(Ds, ldk, a.dout + (long)b * a.L * F + g * dh, a.do_bytes, F, dh, dhp, t0, AT2_TT, AT2_TT, a.dv4);
+    stage_rows_buf<NW>(Kx, ldk, a.v + boff, a.qkv_bytes, (int)a.ld, dh, dhp, t0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+    RelFragT<MAXT> rf;
+    if (a.rel_regs) rel_frag_load<NW>(rf, a.rel, F, g * dh, dh, nchunk);      // (consumed by the last phase: the loads fly under everything else)
+    else stage_rows_buf<NW>(Rx, ldk, a.rel + g * dh, a.rel_bytes, F, dh, dhp, 0, AT_W, 32, a.dv4);
+    for (int idx = tid; idx < AT2_TT * AT2_A3LD; idx += NTHR) A3[idx] = 0.f;
+    stage_wait();
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TPW; ++j) {
+        const int id = wave * TPW + j;
+        if (id < 6) {
+            int rt, ct;
+            win_tile32(id, rt, ct);
+            const f32x4 s = score_tile(Ds + 16 * rt * ldk, Kx + 16 * ct * ldk, ldk, nchunk, i, g4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Sr[(16 * rt + 4 * g4 + r) * AT2_SLD + 16 * ct + i] = s[r];
+        }
+    }
+    __syncthreads();                            // value window dead
+    stage_rows_buf<NW>(Kx, ldk, a.k + boff, a.qkv_bytes, (int)a.ld, dh, dhp, t0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+    for (int t = tid >> 4; t < AT2_TT; t += NTHR / 16) {
+        const int l = tid & 15;
+        const bool rv = t0 + t < a.L;
+        const long arow = (((long)b * a.L + t0 + t) * a.G + g) * AT_W;
+        const float p0 = rv ? a.att[arow + l] : 0.f;
+        const float p1 = (rv && l < 15) ? a.att[arow + l + 16] : 0.f;
+        const float* sr = Sr + t * AT2_SLD;
+        const float d0 = sr[t + l], d1 = l < 15 ? sr[t + l + 16] : 0.f;
+        const float dot = grp16_sum(p0 * d0 + p1 * d1);
+        const float e0 = p0 * (d0 - dot), e1 = p1 * (d1 - dot);
+        float* ar = A3 + t * AT2_A3LD;
+        ar[t + l] = e0;
+        ar[AT2_WINP + l] = e0;
+        if (l < 15) { ar[t + l + 16] = e1; ar[AT2_WINP + l + 16] = e1; }
+        if (rv) {
+            a.de[arow + l] = e0;
+            if (l < 15) a.de[arow + l + 16] = e1;
+        }
+    }
+    stage_wait();
+    __syncthreads();
+    float* dq = a.dq + ((long)b * a.L + t0) * a.dld;
+    if (a.rel_regs) apply32<NW, true>(A3, AT2_A3LD, Kx, ldk, nchunk, dq, a.dld, g * dh, dh, a.L - t0, nullptr, &rf, a.rel_first != 0);
+    else apply32<NW, true>(A3, AT2_A3LD, Kx, ldk, nchunk, dq, a.dld, g * dh, dh, a.L - t0, Rx, nullptr, a.rel_first != 0);
+}
+
+// backward, key/value side for a 32-frame tile of window rows s: the transposed band A4[s][u] = coef[s0-15+u][s - u + 30] (u = 0..61)
+// against the 62-row window of dout / q -- the same band geometry as the forward apply (row tile rt holds entries in chunks rt .. rt+2)
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void attn_bwd_kv32_k(AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NTHR = NW * 64;
+    const int dh = a.dh, dhp = a.dhp, ldk = dhp + 4, nchunk = dhp >> 4, F = a.G * dh;
+    float* Yd = smem;                           // [64][ldk]  dout window (then q window with seq_kv)
+    float* Yq = a.seq_kv ? Yd : Yd + AT2_WINP * ldk;  // [64][ldk]  q window
+    float* Ca = Yq + AT2_WINP * ldk;            // [64][32]   att window
+    float* Ce = Ca + AT2_WINP * 32;             // [64][32]   de window
+    float* A4 = Ce + AT2_WINP * 32;             // [32][68]   transposed band of att
+    float* A5 = A4 + AT2_TT * AT2_A2LD;         // [32][68]   transposed band of de
+    const int ntile = (a.L + AT2_TT - 1) / AT2_TT;
+    const int bx = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = bx / ntile, s0 = (bx - b * ntile) * AT2_TT;
+    const int g = blockIdx.y;
+    const int tid = threadIdx.x;
+    const float* qb = a.q + (long)b * a.L * a.ld + g * dh;
+    stage_rows_buf<NW>(Yd, ldk, a.dout + (long)b * a.L * F + g * dh, a.do_bytes, F, dh, dhp, s0 - AT_P, AT2_WIN, AT2_WINP, a.dv4);
+    if (!a.seq_kv) stage_rows_buf<NW>(Yq, ldk, qb, a.qkv_bytes, (int)a.ld, dh, dhp, s0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+    const int cld = a.G * AT_W;
+    const long coff = (long)b * a.L * cld + g * AT_W;
+    stage_rows_buf<NW>(Ca, 32, a.att + coff, a.co_bytes, cld, AT_W, 32, s0 - AT_P, AT2_WIN, AT2_WINP, false);
+    stage_rows_buf<NW>(Ce, 32, a.de_in + coff, a.co_bytes, cld, AT_W, 32, s0 - AT_P, AT2_WIN, AT2_WINP, false);
+    stage_wait();
+    __syncthreads();
+    for (int idx = tid; idx < AT2_TT * AT2_A2LD; idx += NTHR) {
+        const int sl = idx / AT2_A2LD, u = idx - sl * AT2_A2LD;
+        const int w = sl - u + 2 * AT_P;        // t = s - w + 15  <=>  w = s - t + 15 = sl - u + 30
+        const bool in = u < AT2_WIN && w >= 0 && w < AT_W;
+        A4[idx] = in ? Ca[u * 32 + w] : 0.f;
+        A5[idx] = in ? Ce[u * 32 + w] : 0.f;
+    }
+    __syncthreads();
+    const long orow = ((long)b * a.L + s0) * a.dld;
+    apply32<NW, false>(A4, AT2_A2LD, Yd, ldk, nchunk, a.dv + orow, a.dld, g * dh, dh, a.L - s0);
+    if (a.seq_kv) {
+        __syncthreads();                        // dout window dead
+        stage_rows_buf<NW>(Yq, ldk, qb, a.qkv_bytes, (int)a.ld, dh, dhp, s0 - AT_P, AT2_WIN, AT2_WINP, a.v4);
+        stage_wait();
+        __syncthreads();
+    }
+    apply32<NW, false>(A5, AT2_A2LD, Yq, ldk, nchunk, a.dk + orow, a.dld, g * dh, dh, a.L - s0);
+}
+
 // 16-byte DMA lanes are legal for every fp32 row (the source needs 4-byte alignment only; a row tail of dh % 4 floats goes 4 bytes per lane).
 // RV_ATTN_V4_ALIGNED=1 restores the round-3 rule (16-byte aligned rows of a multiple of four floats) for A/B runs.
 static bool attn_v4(int dh, long ld, const void* p) {
@@ -397,9 +754,37 @@ static int attn_setup(AttnArgs& a, int dh, const char* who) {
         (void)hipFuncSetAttribute((const void*)attn_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)attn_bwd_q_k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)attn_bwd_kv_k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_fwd32_k<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_q32_k<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_kv32_k<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_fwd32_k<10>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_q32_k<10>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_kv32_k<10>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     });
     return RV_OK;
 }
+
+// Frames per workgroup (16 or 32) and waves of the 32-frame form (5 or 10), chosen per head shape by what won in the step
+// (profiles/EXPERIMENTS.md, "attention tiles").  RV_ATTN_TILE=16 / 32 forces one form (16 is the A/B baseline and what
+// tests/test_attn_tiles_gpu.py compares against), RV_ATTN_WAVES=5 / 10 the wave count; RV_ATTN_TILE_WIDE / RV_ATTN_WAVES_WIDE do the
+// same for the wide heads only (dh > 128) and win over the former there.  All are read once, when the library is loaded.
+// The 32-frame form addresses its views with 30-bit offsets (stage_rows_buf): longer views take the 16-frame form.
+static int attn_env(const char* name) { return getenv(name) ? atoi(getenv(name)) : 0; }
+static const int g_attn_tile_env = attn_env("RV_ATTN_TILE"), g_attn_tile_wide_env = attn_env("RV_ATTN_TILE_WIDE");
+static const int g_attn_waves_env = attn_env("RV_ATTN_WAVES"), g_attn_waves_wide_env = attn_env("RV_ATTN_WAVES_WIDE");
+struct AttnForm { int tile, waves; };
+static AttnForm attn_form(int dh, int L, long max_ld) {
+    const bool wide = dh > 128;
+    const int tile = wide && g_attn_tile_wide_env ? g_attn_tile_wide_env : g_attn_tile_env;
+    const int waves = wide && g_attn_waves_wide_env ? g_attn_waves_wide_env : g_attn_waves_env;
+    AttnForm f;
+    f.tile = tile == 16 || tile == 32 ? tile : 32;
+    f.waves = waves == 5 || waves == 10 ? waves : 5;
+    if (((long)L + 64) * max_ld * 4 >= 0x3f000000L) f.tile = 16;
+    return f;
+}
+static unsigned attn_view_bytes(int L, long ld, int dh) { return (unsigned)((((long)L - 1) * ld + dh) * 4); }
+static const size_t kAttnMaxLds = 128 * 1024;
 
 extern "C" {
 
@@ -417,6 +802,19 @@ int rv_local_attn_fwd(const float* q, const float* k, const float* v, long ld, c
     static const int relregs_env = getenv("RV_ATTN_REL_REGS") ? atoi(getenv("RV_ATTN_REL_REGS")) : 1;
     static const size_t occ_kb = getenv("RV_ATTN_OCC_KB") ? (size_t)atoi(getenv("RV_ATTN_OCC_KB")) : 78;      // (experiment: 50 -> three workgroups per CU at dh = 128)
     a.rel_regs = relregs_env && lds > occ_kb * 1024;       // the rel^T block would leave room for only one workgroup per CU
+    const AttnForm form = attn_form(dh, L, ld > (long)G * dh ? ld : (long)G * dh);
+    if (form.tile == 32) {
+        size_t lds32 = ((size_t)(AT2_TT + AT2_WINP + 32) * ldk + AT2_TT * AT2_SLD + AT2_TT * AT2_A2LD) * sizeof(float);
+        a.rel_regs = (relregs_env && lds32 > occ_kb * 1024) || lds32 > kAttnMaxLds;
+        if (a.rel_regs) lds32 -= (size_t)32 * ldk * sizeof(float);
+        a.qkv_bytes = attn_view_bytes(L, ld, dh);
+        a.rel_bytes = attn_view_bytes(AT_W, (long)G * dh, dh);
+        const dim3 grid(B * ((L + AT2_TT - 1) / AT2_TT), G);
+        if (form.waves == 10) hipLaunchKernelGGL((attn_fwd32_k<10>), grid, dim3(640), lds32, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((attn_fwd32_k<5>), grid, dim3(320), lds32, (hipStream_t)stream, a);
+        RV_LAUNCH_CHECK("rv_local_attn_fwd");
+        return RV_OK;
+    }
     if (a.rel_regs) lds -= (size_t)32 * ldk * sizeof(float);
     hipLaunchKernelGGL(attn_fwd_k, dim3(B * ntile, G), dim3(AT_NTHR), lds, (hipStream_t)stream, a);
     RV_LAUNCH_CHECK("rv_local_attn_fwd");
@@ -442,6 +840,30 @@ int rv_local_attn_bwd(const float* dout, const float* q, const float* k, const f
     static const int relregs_env = getenv("RV_ATTN_REL_REGS") ? atoi(getenv("RV_ATTN_REL_REGS")) : 1;
     static const size_t occ_kb = getenv("RV_ATTN_OCC_KB") ? (size_t)atoi(getenv("RV_ATTN_OCC_KB")) : 78;
     a.rel_regs = relregs_env && lds1 > occ_kb * 1024;
+    long max_ld = ld > (long)G * dh ? ld : (long)G * dh;
+    if (max_ld < (long)G * AT_W) max_ld = (long)G * AT_W;
+    const AttnForm form = attn_form(dh, L, max_ld);
+    if (form.tile == 32) {
+        a.rel_first = a.rel_regs;                      // dq accumulates in the order the 16-frame form uses for this head shape
+        size_t q32 = ((size_t)(AT2_TT + AT2_WINP + 32) * ldk + AT2_TT * AT2_SLD + AT2_TT * AT2_A3LD) * sizeof(float);
+        a.rel_regs = (relregs_env && q32 > occ_kb * 1024) || q32 > kAttnMaxLds;
+        if (a.rel_regs) q32 -= (size_t)32 * ldk * sizeof(float);
+        a.qkv_bytes = attn_view_bytes(L, ld, dh);
+        a.do_bytes = attn_view_bytes(L, (long)G * dh, dh);
+        a.rel_bytes = attn_view_bytes(AT_W, (long)G * dh, dh);
+        a.co_bytes = attn_view_bytes(L, (long)G * AT_W, AT_W);
+        const dim3 grid(B * ((L + AT2_TT - 1) / AT2_TT), G), block(form.waves * 64);
+        if (form.waves == 10) hipLaunchKernelGGL((attn_bwd_q32_k<10>), grid, block, q32, st, a);
+        else hipLaunchKernelGGL((attn_bwd_q32_k<5>), grid, block, q32, st, a);
+        RV_LAUNCH_CHECK("rv_local_attn_bwd(q)");
+        const size_t two32 = ((size_t)2 * AT2_WINP * ldk + 2 * AT2_WINP * 32 + 2 * AT2_TT * AT2_A2LD) * sizeof(float);
+        a.seq_kv = two32 > occ_kb * 1024;              // (always so beyond 128 KB: occ_kb is far below)
+        const size_t kv32 = two32 - (a.seq_kv ? (size_t)AT2_WINP * ldk * sizeof(float) : 0);
+        if (form.waves == 10) hipLaunchKernelGGL((attn_bwd_kv32_k<10>), grid, block, kv32, st, a);
+        else hipLaunchKernelGGL((attn_bwd_kv32_k<5>), grid, block, kv32, st, a);
+        RV_LAUNCH_CHECK("rv_local_attn_bwd(kv)");
+        return RV_OK;
+    }
     if (a.rel_regs) lds1 -= (size_t)32 * ldk * sizeof(float);
     hipLaunchKernelGGL(attn_bwd_q_k, dim3(B * ntile, G), dim3(AT_NTHR), lds1, st, a);
     RV_LAUNCH_CHECK("rv_local_attn_bwd(q)");
