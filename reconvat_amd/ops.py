@@ -7,13 +7,14 @@ slice (view) of a wider buffer -- the pixel stride is taken from ``stride(2)``.
 """
 import ctypes
 import os
-import sys
 
 import torch
 from torch.autograd import Function
 
-from . import _lib, plans
+from . import _lib, plans, tuning
 from ._lib import call, invoke, ptr, stream, need_gpu
+# kernel selection lives in tuning.py; tools and tests reach its tables and state through these names (the same objects)
+from .tuning import ALGO_BF16, WINOGRAD_FAMILIES, _algo_cache, _tune_us, _tune_top, _wgrad_tuned, _wgrad_plans, _wgrad_owner, _gemm_splitk  # noqa: F401
 
 SLOPE = 0.01            # F.leaky_relu default (model/UNet_onset.py:197-198)
 BN_MOMENTUM = 0.1       # model/UNet_onset.py:183
@@ -131,10 +132,48 @@ def _keep(obj, fallback):
     (_KEEP_SCOPE[0] if _KEEP_SCOPE[0] is not None else fallback).append(obj)
 
 
+def _fill_pool(pool, n, numel, dtype=torch.uint8):
+    while len(pool) < n:
+        pool.append(torch.empty(numel, dtype=dtype).pin_memory())
+
+
+class _HostTable:
+    """Host side of "fill a table, copy it to the device, run one launch".  No host allocation may happen under hipGraph capture and a captured copy node
+    re-reads its buffer at every replay: a capture takes a pre-pinned buffer from `pool` (prepare_*) that is never recycled and lives, like the device copy,
+    as long as the graph (keep_scope, else `fallback`).  Outside capture: pageable memory, pinned at upload (the pinned allocator is stream-aware)."""
+
+    def __init__(self, what, entry, capacity, pool, fallback, torch_stream, dtype=torch.uint8):
+        self.what, self.entry, self.fallback, self.stream, self.n = what, entry, fallback, torch_stream, 0
+        self.pinned = torch.cuda.is_current_stream_capturing()
+        if self.pinned:
+            if not pool:
+                raise RuntimeError(f'{what}: no pinned table left for hipGraph capture')
+            self.host = pool.pop()
+            _keep(self.host, fallback)
+        else:
+            self.host = torch.empty(capacity * entry, dtype=dtype)
+        self.capacity = self.host.numel() // entry
+
+    def slot(self):
+        """Host address of the next entry (the caller fills it, then counts it in `n`)."""
+        if self.n >= self.capacity:
+            raise RuntimeError(f'{self.what}: table full')
+        return self.host.data_ptr() + self.n * self.entry * self.host.element_size()
+
+    def upload(self):
+        """Device copy of the n filled entries, enqueued on the table's stream (which must be the current one); the table is empty afterwards."""
+        used = self.host[:self.n * self.entry]
+        table = (used if self.pinned else used.pin_memory()).to(self.stream.device, non_blocking=True)
+        table.record_stream(self.stream)
+        if self.pinned:
+            _keep(table, self.fallback)        # captured: keep the device copy's memory out of the graph pool's reuse
+        self.n = 0
+        return table
+
+
 def prepare_replay_pool(n=4):
     """Pinned staging buffers for replay_bn_updates under hipGraph capture (call outside capture)."""
-    while len(_REPLAY_POOL) < n:
-        _REPLAY_POOL.append(torch.empty(4096, dtype=torch.int64).pin_memory())
+    _fill_pool(_REPLAY_POOL, n, 4096, torch.int64)
 
 
 def replay_bn_updates(pendings, device):
@@ -157,25 +196,13 @@ def replay_bn_updates(pendings, device):
         head += [rm, rv, nbt, c, len(coefs), len(lst)]
         coefs += lst
     words = head + coefs
-    # pinned staging buffers are allocated ahead of time (no host allocation may happen under hipGraph capture); a
-    # captured copy node re-reads its buffer at every replay, so buffers used under capture are never recycled
-    capturing = torch.cuda.is_current_stream_capturing()
-    if capturing:
-        if not _REPLAY_POOL:
-            raise RuntimeError('replay_bn_updates: no pinned staging buffer left for hipGraph capture')
-        host = _REPLAY_POOL.pop()
-        _keep(host, _REPLAY_KEEP)
-        assert len(words) <= host.numel(), 'BatchNorm replay table larger than the staging buffer'
-        host[:len(words)] = torch.tensor(words, dtype=torch.int64)
-    else:
+    if not torch.cuda.is_current_stream_capturing():
         prepare_replay_pool()
-        host = torch.tensor(words, dtype=torch.int64).pin_memory()      # (the pinned allocator is stream-aware)
-    table = host[:len(words)].to(device, non_blocking=True)
-    call('rv_bn_running_update_table', ptr(table), len(order), BN_MOMENTUM, stream())
-    table.record_stream(torch.cuda.current_stream(device))
-    if capturing:
-        _keep(table, _REPLAY_KEEP)             # keep the device copy's memory out of the graph pool's reuse
-
+    tab = _HostTable('replay_bn_updates', 1, len(words), _REPLAY_POOL, _REPLAY_KEEP, torch.cuda.current_stream(device), torch.int64)
+    assert len(words) <= tab.capacity, 'BatchNorm replay table larger than the staging buffer'
+    tab.host[:len(words)] = torch.tensor(words, dtype=torch.int64)
+    tab.n = len(words)
+    call('rv_bn_running_update_table', ptr(tab.upload()), len(order), BN_MOMENTUM, stream())
 
 
 class direct_param_grads:
@@ -285,13 +312,23 @@ def _pack_put(key, val):
         del _pack_cache[next(iter(_pack_cache))]
 
 
-def _pack(kind, w, which):
-    """Packed weight fragments for `which` in {'fwd', 'dgrad'} (cached per weight version)."""
-    key = (w.data_ptr(), kind, which)
+def _cached(key, w, make):
+    """The packed copy of the weight (view) `w` under `key`, repacked when the weight changed: make() -> (packed tensor, rv_pack_weights arguments)."""
     tag = (_EPOCH[0], w._version, tuple(w.shape))
     hit = _pack_cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
+    if hit is None or hit[0] != tag:
+        out, args = make()
+        hit = (tag, out, w, args)
+        _pack_put(key, hit)
+    return hit[1]
+
+
+def _pack(kind, w, which):
+    """Packed weight fragments for `which` in {'fwd', 'dgrad'} (cached per weight version)."""
+    return _cached((w.data_ptr(), kind, which), w, lambda: _pack_make(kind, w, which))
+
+
+def _pack_make(kind, w, which):
     cin, cout = _channels(kind, w)
     scatter = 0
     if kind == 'c3':
@@ -318,22 +355,21 @@ def _pack(kind, w, which):
     n = lib.rv_packed_weight_floats(taps, kdim, ndim)
     out = torch.empty(n, device=w.device, dtype=torch.float32)
     call('rv_pack_weights', ptr(w), ptr(out), taps, kdim, ndim, s_k, s_n, flip, scatter, plain, stream())
-    _pack_put(key, (tag, out, w, (taps, kdim, ndim, s_k, s_n, flip, scatter, plain)))
-    return out
+    return out, (taps, kdim, ndim, s_k, s_n, flip, scatter, plain)
+
+
+def _pack_plain(w, tag, args, numel):
+    """Plain [tap][k][n] re-indexed copy of a weight (view) through the packed-weight cache, keyed (pointer, *tag) (part of the PackPlan table)."""
+    def make():
+        out = torch.empty(numel, device=w.device, dtype=torch.float32)
+        call('rv_pack_weights', ptr(w), ptr(out), *args, stream())
+        return out, args
+    return _cached((w.data_ptr(),) + tag, w, make)
 
 
 def _pack_rel(rel, f):
     """rel^T [31, F] for the attention kernels (cached per weight version; part of the PackPlan table)."""
-    key = (rel.data_ptr(), 'rel', 'T')
-    tag = (_EPOCH[0], rel._version, tuple(rel.shape))
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1]
-    args = (1, 31, f, 1, 31, 0, 0, 1)            # out[w*F + c] = rel[c*31 + w]
-    out = torch.empty(31 * f, device=rel.device, dtype=torch.float32)
-    call('rv_pack_weights', ptr(rel), ptr(out), *args, stream())
-    _pack_put(key, (tag, out, rel, args))
-    return out
+    return _pack_plain(rel, ('rel', 'T'), (1, 31, f, 1, 31, 0, 0, 1), 31 * f)            # out[w*F + c] = rel[c*31 + w]
 
 
 def _lin_t(w2d):
@@ -342,16 +378,7 @@ def _lin_t(w2d):
     (rv_gemm's LDS-DMA kernel) instead of gathering W column-wise."""
     n, k = w2d.shape
     assert w2d.stride(1) == 1 and w2d.stride(0) == k
-    key = (w2d.data_ptr(), 'lin', 'T', n, k)
-    tag = (_EPOCH[0], w2d._version, (n, k))
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0] == tag:
-        return hit[1].view(k, n)
-    args = (1, k, n, 1, k, 0, 0, 1)              # out[kk*n + nn] = w[kk + nn*k]
-    out = torch.empty(k * n, device=w2d.device, dtype=torch.float32)
-    call('rv_pack_weights', ptr(w2d), ptr(out), *args, stream())
-    _pack_put(key, (tag, out, w2d, args))
-    return out.view(k, n)
+    return _pack_plain(w2d, ('lin', 'T', n, k), (1, k, n, 1, k, 0, 0, 1), k * n).view(k, n)            # out[kk*n + nn] = w[kk + nn*k]
 
 
 class PackPlan:
@@ -390,13 +417,7 @@ _FWD_MODE = {'c3': 0, 't3': 0, 'c1': 1, 'down': 2, 'up': 3}
 _DGRAD_MODE = {'c3': 0, 't3': 0, 'c1': 1, 'down': 3, 'up': 2}
 
 
-_algo_cache = {}
-_tune_us = {}             # ('conv' | 'wgrad', key) -> microseconds the on-line tuner measured for its choice
-_tune_top = {}            # ('conv', key) -> [(us, algo)] the three fastest candidates (tools/tune_plans.py --in-situ re-ranks near ties in the step)
-_algo_unchecked = set()    # table entries borrowed from another batch size: legality is checked by their first launch
-# 'table' (default): the shipped per-shape plan table (reconvat_amd/plans.py, tuned_plans.json) -- what bench.py, the scripts and
-# the -m gpu tests all run; True (RV_AUTOTUNE=1): time every legal tile on the first eager call of a shape (how the table is
-# made, tools/tune_plans.py); False (RV_AUTOTUNE=0): library default tiles.
+# 'table' (default): the shipped plan table; True: on-line tuning; False: library default tiles (plans.py).  Read at call time and handed to tuning.py.
 AUTOTUNE = plans.default_mode()
 
 
@@ -407,10 +428,6 @@ AUTOTUNE = plans.default_mode()
 # (tools/bf16_emulation.py): 'fwd' breaks the 1e-3 forward parity bar (frame2 moves by 18 %), 'bwd' leaves every
 # loss term and posteriorgram bit-identical and moves the gradients by 0.6 % -- so only 'bwd' is meant to be used.
 BF16 = {'fwd': False, 'bwd': False}
-ALGO_BF16 = 1 << 20
-# algo families (bits 8..11) that are fp32 Winograd tiles -- conv3x3_wino_k (0x6 / 0xA / 0xC) and the software-pipelined conv3x3_wino2_k
-# (0x8 / 0x9 / 0xB / 0xD): no bf16-operand form, a bf16 launch of such a shape runs the library-default direct tile instead
-WINOGRAD_FAMILIES = (6, 8, 9, 10, 11, 12, 13, 14)
 
 
 class bf16_final_graphs:
@@ -427,136 +444,44 @@ class bf16_final_graphs:
 
 
 def _conv_call(mode, x, ild, bb, h, wd, cin, out, old, ho, wo, cout, wpack, bias, stats=None, bnbwd=None, accumulate=False, bf16=False):
-    """rv_conv_fwd with a per-shape choice between the LDS-free and the LDS/DMA-pipelined 3x3 kernel.  The first
-    eager call of a shape times both (HIP events on the launch stream) and caches the winner; under hipGraph
-    capture an untuned shape uses the library default.  ``stats`` (fp64 [2*cout], zeroed): the conv also leaves the
-    BatchNorm batch statistics of its output there (fused epilogue of the persistent kernel, else a statistics pass
-    -- the tuner times whichever the candidate implies).  ``bnbwd`` = (z, coef, slope): the call is an input gradient
-    and ``stats`` receives the backward reduction of the BatchNorm whose output gradient is being produced."""
+    """rv_conv_fwd with the per-shape tile choice of tuning.choose_conv (plan table; ops.AUTOTUNE = True: the first eager call of a shape times every
+    candidate tile and caches the winner; under hipGraph capture an untuned shape uses the library default).  ``stats`` (fp64 [2*cout], zeroed): the
+    conv also leaves the BatchNorm batch statistics of its output there (fused epilogue of the persistent kernel, else a statistics pass -- the tuner
+    times whichever the candidate implies).  ``bnbwd`` = (z, coef, slope): the call is an input gradient and ``stats`` receives the backward
+    reduction of the BatchNorm whose output gradient is being produced."""
     args = (mode, ptr(x), ild, bb, h, wd, cin, ptr(out), old, ho, wo, cout, ptr(wpack), ptr(bias), 1 if accumulate else 0)
     if bnbwd is not None:
         bz, bcoef, bslope = bnbwd
         tail = (ptr(bz), _geom(bz)[4], ptr(bcoef), float(bslope))
     else:
         tail = (None, 0, None, 0.0)
-    algo = 0
-    if os.environ.get('RV_FORCE_ALGO') and (mode == 0 or os.environ.get('RV_FORCE_ALGO_ALL')):   # kernel experiments
-        algo = int(os.environ['RV_FORCE_ALGO'], 0)
-    elif AUTOTUNE and cin % 8 == 0 and (cout > 2 or mode == 3):     # (the small-channel VALU kernels have one form)
-        base_key = (mode, bb, h, wd, cin, cout, ild, old, stats is not None, bnbwd is not None)
-        # the bf16-operand variant of a shape is its own cache entry in every mode: its tile may differ from the fp32 one (the fp32
-        # Winograd tiles have no bf16 form), and a bf16 launch must never overwrite what the fp32 launches of the same shape run
-        key = base_key + ('bf16',) if bf16 else base_key
-        algo = _algo_cache.get(key, -1)
-        if algo < 0 and AUTOTUNE == 'table':
-            hit = plans.lookup_conv(base_key)
-            algo = hit[0] if hit is not None else 0
-            if bf16 and (algo >> 8) & 15 in WINOGRAD_FAMILIES:
-                algo = 0                        # fp32 Winograd tile: the bf16 launch of this shape runs the library-default direct tile
-            _algo_cache[key] = algo
-            if hit is not None and not hit[1] and algo != 0:
-                _algo_unchecked.add(key)
-        if algo < 0:
-            if torch.cuda.is_current_stream_capturing():
-                algo = 0
-            else:
-                best, algo = None, 0
-                st = torch.cuda.current_stream()
-                lib = _lib.load()
-                ntile_n = (4 * cout if mode == 3 else cout + 15) // 16
-                bfbit = ALGO_BF16 if bf16 else 0
-                scratch = ptr(torch.zeros_like(stats)) if stats is not None else None
-                targs = args
-                if accumulate:          # the timing runs must not touch the buffer that is being accumulated into
-                    tmp_out = torch.empty(bb * ho * wo * old, device=out.device, dtype=torch.float32)
-                    targs = args[:7] + (ptr(tmp_out),) + args[8:14] + (0,)
-                cands = [1, 2] if mode == 0 else [0]
-                for nt in (1, 2, 3, 4):
-                    if ntile_n % nt:
-                        continue
-                    cands += [0x100 | nt << 4 | mt for mt in (1, 2, 4)]     # direct kernel (every mode)
-                    if mode != 0:                                           # ... with the K loop split over the four waves (deep layers)
-                        cands += [0x500 | nt << 4 | mt for mt in (1, 2, 4) if nt * mt <= 4]
-                    if mode == 0:                                           # persistent LDS kernel, 4 / 8 / 16 waves
-                        cands += [0x200 | nt << 4 | mt for mt in (1, 2, 4, 8)]
-                        cands += [0x300 | nt << 4 | mt for mt in (1, 2, 4)]
-                        cands += [0x400 | nt << 4 | mt for mt in (1, 2, 4)]
-                        cands += [0x700 | nt << 4 | mt for mt in (1, 2, 3, 4, 5, 6)]     # 12 waves: 3 .. 18 tiles per SIMD and band
-                if mode == 0:
-                    # rows per band: the tile slots of a (waves, MTW) pair hold th_max rows; fewer rows trade padding for a band
-                    # count that divides over the 256 workgroup slots (the deep layers have only a few bands per image)
-                    extra = []
-                    for cand in cands:
-                        nwv = {2: 4, 3: 8, 4: 16, 7: 12}.get(cand >> 8)
-                        if nwv is None:
-                            continue
-                        th_max = min(h, (cand & 15) * 16 * nwv // wd)
-                        if th_max < 2:
-                            continue
-                        nb0 = -(-h // th_max)
-                        for nb in range(nb0, nb0 + 4):
-                            th = -(-h // nb)
-                            if 0 < th < th_max and th < 256:
-                                extra.append(th << 12 | cand)
-                    cands += sorted(set(extra))
-                    if cin % 16 == 0 and os.environ.get('RV_TUNE_WINOGRAD', '1') != '0':
-                        # Winograd F(2x2,3x3) form (0x6NM: 8 waves; 0xANM / 0xCNM: 8 / 12 waves with the patch read half a chunk at a
-                        # time; bands of an even number of rows).  NT = 2 exists in the half-chunk 8-wave form only.
-                        wt_ = (wd + 1) // 2
-                        for fam, nwv in ((6, 8), (10, 8), (12, 12)):
-                            for nt, mt in ((1, 1), (2, 1)):
-                                if ntile_n % nt or (nt == 2 and fam != 10):
-                                    continue
-                                th_max = min(h, 2 * ((nwv * mt * 16) // wt_))
-                                ths = [0] + [t for t in range(2, th_max, 2) if -(-h // t) != -(-h // (t + 2))]
-                                cands += [t << 12 | fam << 8 | nt << 4 | mt for t in ths]
-                        if os.environ.get('RV_TUNE_WINO2', '1') != '0':
-                            # ... and its software-pipelined form (conv_wino2.hip, round 5): 0x8NM / 0x9NM = 8 waves with the full / half-chunk patch,
-                            # 0xBNM = 4 waves, 0xDNM = 12 waves (half-chunk patch); the taller half of the legal band heights only (short bands lose to their halo)
-                            for fam, nwv, tiles in ((8, 8, ((1, 1),)), (9, 8, ((1, 1), (2, 1), (1, 2))), (11, 4, ((1, 2), (2, 1))), (13, 12, ((1, 1),))):
-                                for nt, mt in tiles:
-                                    if ntile_n % nt:
-                                        continue
-                                    th_max = min(h, 2 * ((nwv * mt * 16) // wt_))
-                                    ths = [0] + [t for t in range(2, th_max, 2) if -(-h // t) != -(-h // (t + 2)) and t >= th_max // 2]
-                                    cands += [t << 12 | fam << 8 | nt << 4 | mt for t in ths]
-                    fams = os.environ.get('RV_TUNE_FAMILIES')          # experiment: restrict the LDS tile families the tuner may pick
-                    if fams:
-                        keep = {int(f, 0) for f in fams.split(',')}
-                        cands = [c for c in cands if ((c >> 8) & 15) in keep or c in (1, 2) and ((1 if c == 1 else 2) in keep)]
-                ranked = []
-                for cand in cands:
-                    if lib.rv_conv_fwd(*targs, cand | bfbit, scratch, *tail, st.cuda_stream) != 0:
-                        continue                                   # tile does not fit this shape
-                    t = None
-                    for _rep in range(2):                          # best of two bursts of three: less timing noise
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(st)
-                        for _ in range(3):
-                            lib.rv_conv_fwd(*targs, cand | bfbit, scratch, *tail, st.cuda_stream)
-                        e1.record(st)
-                        e1.synchronize()
-                        dt = e0.elapsed_time(e1)
-                        t = dt if t is None else min(t, dt)
-                    ranked.append((t / 3 * 1e3, cand))
-                    if best is None or t < best:
-                        best, algo = t, cand
-                _algo_cache[key] = algo
-                if best is not None:
-                    _tune_us[('conv', key)] = best / 3 * 1e3
-                    _tune_top[('conv', key)] = sorted(ranked)[:3]
-                if os.environ.get('RV_TUNE_LOG') and best is not None:
-                    print(f'[tune] conv mode={mode} {cin}->{cout} {h}x{wd} B={bb}: algo={algo:#x} {best / 3 * 1e3:.1f} us', file=sys.stderr)
-        if key in _algo_unchecked:
-            _algo_unchecked.discard(key)
-            if invoke('rv_conv_fwd', *args, algo | (ALGO_BF16 if bf16 else 0), ptr(stats), *tail, stream()) == 0:
-                return
-            algo = _algo_cache[key] = 0         # the borrowed tile does not fit this batch size: library default
-    if bf16 and (algo >> 8) & 15 in WINOGRAD_FAMILIES:
-        algo = 0                                # (forced / on-line tuned Winograd tile: no bf16 form -> library-default direct tile)
-    if bf16 and algo not in (1,) and (algo >> 8) & 15 != 1:
-        algo |= ALGO_BF16                       # (the library ignores the bit outside the persistent 3x3 kernel / 16-channel chunks)
-    call('rv_conv_fwd', *args, algo, ptr(stats), *tail, stream())
+    force = os.environ.get('RV_FORCE_ALGO') and (mode == 0 or os.environ.get('RV_FORCE_ALGO_ALL'))   # kernel experiments
+
+    def online(key):
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        st = torch.cuda.current_stream()
+        lib = _lib.load()
+        scratch = ptr(torch.zeros_like(stats)) if stats is not None else None
+        targs = args
+        if accumulate:          # the timing runs must not touch the buffer that is being accumulated into
+            tmp_out = torch.empty(bb * ho * wo * old, device=out.device, dtype=torch.float32)
+            targs = args[:7] + (ptr(tmp_out),) + args[8:14] + (0,)
+        fams = os.environ.get('RV_TUNE_FAMILIES')
+        cands = tuning.conv_candidates(mode, h, wd, cin, cout, winograd=os.environ.get('RV_TUNE_WINOGRAD', '1') != '0',
+                                       wino2=os.environ.get('RV_TUNE_WINO2', '1') != '0',
+                                       families={int(f, 0) for f in fams.split(',')} if fams else None)
+
+        def run(cand):
+            return lib.rv_conv_fwd(*targs, cand | (ALGO_BF16 if bf16 else 0), scratch, *tail, st.cuda_stream)
+        return tuning.tune('conv', key, cands, run, lambda cand: tuning.best_of_bursts(lambda: run(cand), st),
+                           describe=lambda algo: f'mode={mode} {cin}->{cout} {h}x{wd} B={bb}: algo={algo:#x}')
+
+    algo = tuning.choose_conv(AUTOTUNE, (mode, bb, h, wd, cin, cout, ild, old, stats is not None, bnbwd is not None), bf16,
+                              int(os.environ['RV_FORCE_ALGO'], 0) if force else None, online,
+                              lambda algo: invoke('rv_conv_fwd', *args, algo, ptr(stats), *tail, stream()))
+    if algo is not None:
+        call('rv_conv_fwd', *args, algo, ptr(stats), *tail, stream())
 
 
 def conv_forward_into(kind, x, w, b, out, stats=None, bf16=False):
@@ -627,90 +552,35 @@ class BnLink:
         return self.ws is not None and self.z is not None and tuple(self.z.shape) == tuple(dx.shape)
 
 
-_wgrad_tuned = set()       # (taps, B, Hv, Wv, Ca, Cb): shapes whose partition this process has decided
-_wgrad_plans = {}          # (taps, B, Hv, Wv, Ca, Cb) -> (nw, wgs): what this process pinned in the library (tools/tune_plans.py dumps it)
-# The library keys its partition by (taps, B, Hv, Ca, Cb), without the row width Wv: shapes that differ only in width -- the same layer of a
-# 229-bin and of a 176-bin model -- share ONE library entry.  _wgrad_owner records which full shape last pinned each entry; a launch of another
-# width re-pins the entry to its own plan (or the library default) first, so no shape runs the partition decided for another width.
-_wgrad_owner = {}          # (taps, B, Hv, Ca, Cb) -> (taps, B, Hv, Wv, Ca, Cb)
-
-
-def _pin_wgrad(lib, full, plan):
-    """Pin `plan` ((nw, wgs); None = library default) for the full shape `full` and record it as the owner of its library entry."""
-    taps, bb, hv, _, ca, cb = full
-    if lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *(plan if plan is not None else (0, 0))) != 0:
-        return False
-    _wgrad_owner[(taps, bb, hv, ca, cb)] = full
-    return True
-
-
-def _repin_wgrad(lib, full):
-    """Before a launch of the shape `full`: if another width pinned the shared library entry since, restore this shape's plan.
-    Host-only (legal under hipGraph capture); a no-op while one width uses the entry, i.e. for every launch of a single model."""
-    taps, bb, hv, _, ca, cb = full
-    owner = _wgrad_owner.get((taps, bb, hv, ca, cb))
-    if owner is not None and owner != full:
-        _pin_wgrad(lib, full, _wgrad_plans.get(full))
-
-
 def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, s_a, s_b, flip):
-    """Per-shape partition of the MFMA weight-gradient kernel (waves per workgroup x workgroups on the chip): the first eager
-    call of a shape times the candidates (HIP events on the launch stream, scratch outputs) and pins the winner in the library
-    (rv_conv_wgrad_set_plan); under hipGraph capture an untuned shape keeps the library default (8 waves, 256 workgroups)."""
+    """Per-shape partition of the MFMA weight-gradient kernel (waves per workgroup x workgroups on the chip): the plan table's, or the first eager call of a shape
+    times the candidates (scratch outputs) and pins the winner (rv_conv_wgrad_set_plan); under hipGraph capture an untuned shape keeps the library default."""
     key = (taps, bb, hv, wv, ca, cb)
     if not AUTOTUNE or ca * cb * taps <= 144 or ca == 1:
         return
-    if key in _wgrad_tuned:
-        _repin_wgrad(lib, key)
-        return
-    if AUTOTUNE == 'table':
-        # host-only (legal under hipGraph capture); runs before the first launch of the shape, i.e. never between a deferred
-        # weight-gradient launch of that shape and its table flush
-        _wgrad_tuned.add(key)
-        plan = plans.lookup_wgrad(key)
-        if plan is not None and _pin_wgrad(lib, key, plan):
-            _wgrad_plans[key] = plan
-        else:
-            _repin_wgrad(lib, key)
-        return
+    if AUTOTUNE == 'table' or key in tuning._wgrad_tuned:
+        # (runs before the first launch of the shape, i.e. never between a deferred weight-gradient launch of that shape and its table flush)
+        return tuning.wgrad_plan_for(lib, key, AUTOTUNE)
     if torch.cuda.is_current_stream_capturing():
-        _repin_wgrad(lib, key)
-        return
-    _wgrad_tuned.add(key)
+        return tuning._repin_wgrad(lib, key)
+    tuning._wgrad_tuned.add(key)
     st = torch.cuda.current_stream()
     dw = torch.empty_like(w)
     db = torch.empty(cb, device=w.device, dtype=torch.float32)
-    best, choice = None, (0, 0)
-    cands = [(8, 256), (8, 512), (4, 256), (4, 512), (8, 128), (8, 1024)]
-    if taps == 9 and hv % 2 == 0 and os.environ.get('RV_TUNE_WGRAD_WINO', '1') != '0':
-        cands += [(24, 256), (24, 512), (24, 128)]          # nw = 24: eight waves, Winograd F(3x3, 2x2) form (wgrad_wino_k)
-    for nw, wgs in cands:
-        if lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, nw, wgs) != 0:
-            continue
+    held = []
+
+    def try_plan(plan):
+        if lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *plan) != 0:
+            return 1
         nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, bb, hv, ca, cb)
         ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-        args = (mode, ptr(u), uld, hu, wu, ca, ptr(v), vld, hv, wv, cb, bb, ptr(dw), s_a, s_b, flip, ptr(db), 0, ptr(ws), nbytes,
-                st.cuda_stream)
-        if lib.rv_conv_wgrad(*args) != 0:
-            continue
-        t = None
-        for _rep in range(2):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(3):
-                lib.rv_conv_wgrad(*args)
-            e1.record(st)
-            e1.synchronize()
-            dt = e0.elapsed_time(e1)
-            t = dt if t is None else min(t, dt)
-        if best is None or t < best:
-            best, choice = t, (nw, wgs)
-    _pin_wgrad(lib, key, choice)
-    _wgrad_plans[key] = choice
-    if best is not None:
-        _tune_us[('wgrad', (taps, bb, hv, wv, ca, cb))] = best / 3 * 1e3
-    if os.environ.get('RV_TUNE_LOG'):
-        print(f'[tune] wgrad taps={taps} {ca}->{cb} {hv}x{wv} B={bb}: nw={choice[0]} wgs={choice[1]} {best / 3 * 1e3:.1f} us', file=sys.stderr)
+        held[:] = [(mode, ptr(u), uld, hu, wu, ca, ptr(v), vld, hv, wv, cb, bb, ptr(dw), s_a, s_b, flip, ptr(db), 0, ptr(ws), nbytes, st.cuda_stream), ws]
+        return lib.rv_conv_wgrad(*held[0])
+    choice = tuning.tune('wgrad', key, tuning.wgrad_candidates(taps, hv, winograd=os.environ.get('RV_TUNE_WGRAD_WINO', '1') != '0'), try_plan,
+                         lambda plan: tuning.best_of_bursts(lambda: lib.rv_conv_wgrad(*held[0]), st), default=(0, 0),
+                         describe=lambda c: f'taps={taps} {ca}->{cb} {hv}x{wv} B={bb}: nw={c[0]} wgs={c[1]}')
+    tuning._pin_wgrad(lib, key, choice)
+    tuning._wgrad_plans[key] = choice
 
 
 def _wgrad_geom(kind, x, dy, w, bf16):
@@ -811,17 +681,10 @@ def conv_wgrad_merged(items):
     if n == 1 or not same:
         return False
     tkey = (taps, n * bb, hv, wv, ca, cb)
-    if AUTOTUNE and tkey not in _wgrad_tuned:
+    if AUTOTUNE:
         # the partition of n * bb images: the table's entry (or the nearest batch's), else the one this process tuned for one pass -- never the
         # on-line tuner's timing launches (they read n * bb CONTIGUOUS images from the first segment)
-        _wgrad_tuned.add(tkey)
-        plan = (plans.lookup_wgrad(tkey) if AUTOTUNE == 'table' else None) or _wgrad_plans.get((taps, bb, hv, wv, ca, cb))
-        if plan is not None and _pin_wgrad(lib, tkey, tuple(plan)):
-            _wgrad_plans[tkey] = tuple(plan)
-        else:
-            _repin_wgrad(lib, tkey)
-    elif AUTOTUNE:
-        _repin_wgrad(lib, tkey)
+        tuning.wgrad_plan_for(lib, tkey, AUTOTUNE, (taps, bb, hv, wv, ca, cb))
     nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, n * bb, hv, ca, cb)
     ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
     us = (ctypes.c_void_p * n)(*[g[2].data_ptr() for g in geo])
@@ -993,63 +856,45 @@ _WGRAD_MAX = 512           # entries per table
 
 def prepare_wgrad_tables(n=3):
     """Pinned host tables for deferred_wgrad_reductions under hipGraph capture (call outside capture)."""
-    eb = _lib.load().rv_wgrad_table_entry_bytes()
-    while len(_WGRAD_POOL) < n:
-        _WGRAD_POOL.append(torch.empty(_WGRAD_MAX * eb, dtype=torch.uint8).pin_memory())
+    _fill_pool(_WGRAD_POOL, n, _WGRAD_MAX * _lib.load().rv_wgrad_table_entry_bytes())
 
 
-class _WgradTable:
+class _WgradTable(_HostTable):
     def __init__(self, device, torch_stream):
-        self.eb = _lib.load().rv_wgrad_table_entry_bytes()
-        self.device, self.stream, self.n, self.keep = device, torch_stream, 0, []
-        if torch.cuda.is_current_stream_capturing():
-            if not _WGRAD_POOL:
-                raise RuntimeError('deferred_wgrad_reductions: no pinned table left for hipGraph capture')
-            self.host = _WGRAD_POOL.pop()
-            _keep(self.host, _WGRAD_KEEP)
-            self.pinned = True
-        else:
-            self.host = torch.empty(_WGRAD_MAX * self.eb, dtype=torch.uint8)
-            self.pinned = False
-
-    def slot(self):
-        if self.n >= _WGRAD_MAX:
-            raise RuntimeError('deferred_wgrad_reductions: table full')
-        return self.host.data_ptr() + self.n * self.eb
+        super().__init__('deferred_wgrad_reductions', _lib.load().rv_wgrad_table_entry_bytes(), _WGRAD_MAX, _WGRAD_POOL, _WGRAD_KEEP, torch_stream)
+        self.keep = []
 
     def flush(self):
         if self.n == 0:
             return
-        lib = _lib.load()
-        total = lib.rv_wgrad_table_finalize(self.host.data_ptr(), self.n)
-        used = self.host[:self.n * self.eb]
+        n, total = self.n, _lib.load().rv_wgrad_table_finalize(self.host.data_ptr(), self.n)
         with torch.cuda.stream(self.stream):
-            src = used if self.pinned else used.pin_memory()
-            table = src.to(self.device, non_blocking=True)
-            call('rv_wgrad_reduce_table', ptr(table), self.n, total, self.stream.cuda_stream)
-            table.record_stream(self.stream)
-            if self.pinned:
-                _keep(table, _WGRAD_KEEP)      # captured: keep the device copy's memory out of the graph pool's reuse
-        self.n, self.keep = 0, []
+            call('rv_wgrad_reduce_table', ptr(self.upload()), n, total, self.stream.cuda_stream)
+        self.keep = []
 
 
-class deferred_wgrad_reductions:
-    """While active, conv weight-gradient calls that accumulate into param.grad launch only their partial-sum kernel; the
-    reductions of ALL layers run as one launch per stream at ``flush()`` (call it after backward, before the gradients are
-    read).  One reduction launch per layer is launch-latency bound (161 launches of ~5 us per step)."""
+class _deferred:
+    """Base of the deferred_* contexts: while active, the module's one-element list `slot` exposes the {key: table} dict the launches fill."""
 
     def __enter__(self):
-        self.prev = _WGRAD_DEFER[0]
+        self.prev = self.slot[0]
         self.tables = {}
-        _WGRAD_DEFER[0] = self.tables
+        self.slot[0] = self.tables
         return self
 
     def __exit__(self, *exc):
-        _WGRAD_DEFER[0] = self.prev
+        self.slot[0] = self.prev
 
     def flush(self):
         for t in self.tables.values():
             t.flush()
+
+
+class deferred_wgrad_reductions(_deferred):
+    """While active, conv weight-gradient calls that accumulate into param.grad launch only their partial-sum kernel; the
+    reductions of ALL layers run as one launch per stream at ``flush()`` (call it after backward, before the gradients are
+    read).  One reduction launch per layer is launch-latency bound (161 launches of ~5 us per step)."""
+    slot = _WGRAD_DEFER
 
 
 def _out_hw(kind, h, w, size):
@@ -1220,7 +1065,7 @@ def skip_conv_ksplit(x, cout):
         return False                         # not in the table: library default tile
     if not hit[1]:
         return None                          # borrowed from another batch size: its legality is only known after the first launch
-    return ((hit[0] >> 8) & 15) == 5
+    return tuning.decode(hit[0])[0] in tuning.KSPLIT_FAMILIES
 
 
 class BnActFn(Function):
@@ -1343,43 +1188,12 @@ def _mat(t):
     return ptr(t), t.shape[0], t.shape[1], t.stride(0), t.stride(1)
 
 
-_gemm_splitk = {}          # (M, N, K, batch, A k-fast, B k-fast, act, accumulate) -> split-K factor in use
-
-
 def _splitk_for(m_out, n_out, k):
     """Library-default split-K heuristic (shapes outside the plan table): enough workgroups to cover the chip twice."""
     blocks = ((m_out + 63) // 64) * ((n_out + 63) // 64)
     if blocks >= 256 or k < 512:
         return 1
     return max(1, min(16, 512 // blocks, k // 128))
-
-
-def _tune_gemm(key, launch, m, n, k, cands=(1, 2, 3, 4, 6, 8, 12, 16, 24, 32)):
-    """Time the split-K candidates of one GEMM shape (HIP events on the launch stream, scratch output) and keep the fastest.
-    Split-K is deterministic for a given factor (in-order fold), so the choice only fixes the summation grouping."""
-    st = torch.cuda.current_stream()
-    blocks = ((m + 63) // 64) * ((n + 63) // 64)
-    best, choice = None, 1
-    for s in cands:
-        if s > 1 and (k // s < 64 or blocks * s > 4096):
-            continue
-        launch(s)
-        t = None
-        for _rep in range(2):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            for _ in range(3):
-                launch(s)
-            e1.record(st)
-            e1.synchronize()
-            dt = e0.elapsed_time(e1)
-            t = dt if t is None else min(t, dt)
-        if best is None or t < best * 0.97:               # a larger factor must win by 3 %: ties go to fewer slices
-            best, choice = t, s
-    _tune_us[('gemm', key)] = best / 3 * 1e3
-    if os.environ.get('RV_TUNE_LOG'):
-        print(f'[tune] gemm {key}: splitk={choice} {best / 3 * 1e3:.1f} us', file=sys.stderr)
-    return choice
 
 
 def gemm(a, b_kn, c, bias=None, act=0, accumulate=False, splitk=None, c2=None, batch=1, bstrides=(0, 0, 0), a_rowsum=None,
@@ -1411,7 +1225,7 @@ def gemm(a, b_kn, c, bias=None, act=0, accumulate=False, splitk=None, c2=None, b
     deferrable = defer_ok and accumulate and not deterministic and bias is None and act == 0 and c2 is None and _GEMM_DEFER[0] is not None
     if splitk is None:
         key = (m, n, k, batch, int(sak <= sam), int(sbk <= sbn), act, int(bool(accumulate)) + 2 * int(bool(deterministic)))
-        splitk = _gemm_splitk.get(key)
+        splitk = tuning._gemm_splitk.get(key)
         if splitk is None:
             if AUTOTUNE == 'table':
                 splitk = plans.lookup_gemm(key)
@@ -1420,11 +1234,15 @@ def gemm(a, b_kn, c, bias=None, act=0, accumulate=False, splitk=None, c2=None, b
                 extent = (m - 1) * scm + (n - 1) * scn + 1 + (batch - 1) * bstrides[2]
                 tmp = torch.zeros(extent, device=c.device, dtype=torch.float32)
                 rs_tmp = torch.zeros(m, device=c.device, dtype=torch.float32) if a_rowsum is not None else None
-                splitk = _tune_gemm(key, lambda s: launch(s, ptr(tmp), ptr(rs_tmp)), m, n, k,
-                                    (1, 2, 3, 4, 6, 8, 12, 16, 24, 32) if (deterministic or act == 0) else (1,))
+                # (split-K is deterministic for a given factor -- in-order fold --, so the choice only fixes the summation grouping)
+                cands = tuning.gemm_splitk_candidates(m, n, k, (1, 2, 3, 4, 6, 8, 12, 16, 24, 32) if (deterministic or act == 0) else (1,))
+                st = torch.cuda.current_stream()
+                splitk = tuning.tune('gemm', key, cands, lambda s: launch(s, ptr(tmp), ptr(rs_tmp)) or 0,
+                                     lambda s: tuning.best_of_bursts(lambda: launch(s, ptr(tmp), ptr(rs_tmp)), st),
+                                     tuning.faster_by_3_percent, default=1, describe=lambda s: f'{key}: splitk={s}')
             if splitk is None:
                 splitk = _splitk_for(m, n, k)
-            _gemm_splitk[key] = splitk
+            tuning._gemm_splitk[key] = splitk
     if deferrable and _defer_gemm(a, b_kn, c, splitk, batch, bstrides, a_rowsum):
         return
     launch(splitk)
@@ -1443,65 +1261,37 @@ GEMM_TABLE_WORK = {}       # device table pointer -> (flops, algorithmic bytes) 
 
 def prepare_gemm_tables(n=3):
     """Pinned host tables for deferred_param_gemms under hipGraph capture (call outside capture)."""
-    eb = _lib.load().rv_gemm_table_entry_bytes()
-    while len(_GEMM_POOL) < n:
-        _GEMM_POOL.append(torch.empty(_GEMM_MAX * eb, dtype=torch.uint8).pin_memory())
+    _fill_pool(_GEMM_POOL, n, _GEMM_MAX * _lib.load().rv_gemm_table_entry_bytes())
 
 
-class _GemmTable:
+class _GemmTable(_HostTable):
     """The pending accumulating GEMMs of one (stream, operand orientation)."""
 
     def __init__(self, device, torch_stream, orientation):
-        self.eb = _lib.load().rv_gemm_table_entry_bytes()
-        self.device, self.stream, self.orientation, self.n, self.keep = device, torch_stream, orientation, 0, []
+        super().__init__('deferred_param_gemms', _lib.load().rv_gemm_table_entry_bytes(), _GEMM_MAX, _GEMM_POOL, _GEMM_KEEP, torch_stream)
+        self.orientation, self.keep = orientation, []
         self.flops = self.bytes = 0.0
-        if torch.cuda.is_current_stream_capturing():
-            if not _GEMM_POOL:
-                raise RuntimeError('deferred_param_gemms: no pinned table left for hipGraph capture')
-            self.host = _GEMM_POOL.pop()
-            _keep(self.host, _GEMM_KEEP)
-            self.pinned = True
-        else:
-            self.host = torch.empty(_GEMM_MAX * self.eb, dtype=torch.uint8)
-            self.pinned = False
 
     def flush(self):
         if self.n == 0:
             return
         fold = ctypes.c_long(0)
-        total = _lib.load().rv_gemm_table_finalize(self.host.data_ptr(), self.n, ctypes.addressof(fold))
-        used = self.host[:self.n * self.eb]
+        n, total = self.n, _lib.load().rv_gemm_table_finalize(self.host.data_ptr(), self.n, ctypes.addressof(fold))
         with torch.cuda.stream(self.stream):
-            src = used if self.pinned else used.pin_memory()
-            table = src.to(self.device, non_blocking=True)
-            call('rv_gemm_table_run', ptr(table), self.n, total, fold.value, self.orientation, self.stream.cuda_stream)
-            table.record_stream(self.stream)
-            if self.pinned:
-                _keep(table, _GEMM_KEEP)       # captured: keep the device copy's memory out of the graph pool's reuse
+            table = self.upload()
+            call('rv_gemm_table_run', ptr(table), n, total, fold.value, self.orientation, self.stream.cuda_stream)
             if KEEP_TABLES[0]:
                 _GEMM_KEEP.append((table, self.keep))
                 GEMM_TABLE_WORK[table.data_ptr()] = (self.flops, self.bytes)
-        self.n, self.keep = 0, []
+        self.keep = []
         self.flops = self.bytes = 0.0
 
 
-class deferred_param_gemms:
+class deferred_param_gemms(_deferred):
     """While active, linear-layer / attention parameter-gradient GEMMs that accumulate into param.grad are only REGISTERED; all of
     them run as one grouped launch per stream at ``flush()`` (after backward, before the gradients are read).  Alone each of them
     is a few dozen workgroups with a 5 120-long reduction: latency-bound, 25-90 us; side by side they fill the chip."""
-
-    def __enter__(self):
-        self.prev = _GEMM_DEFER[0]
-        self.tables = {}
-        _GEMM_DEFER[0] = self.tables
-        return self
-
-    def __exit__(self, *exc):
-        _GEMM_DEFER[0] = self.prev
-
-    def flush(self):
-        for t in self.tables.values():
-            t.flush()
+    slot = _GEMM_DEFER
 
 
 _TABLE_PARK = os.environ.get('RV_GEMM_TABLE_PARK', '1') != '0'      # (0: every k slice of a grouped GEMM adds atomically, the form until round 5)
@@ -1521,13 +1311,13 @@ def _defer_gemm(a, b_kn, c, splitk, batch, bstrides, a_rowsum):
     tab = tables.get(key)
     if tab is None:
         tab = tables[key] = _GemmTable(c.device, cur, orient)
-    if tab.n >= _GEMM_MAX:
+    if tab.n >= tab.capacity:
         return False
     lib = _lib.load()
     # split-K inside the grouped launch: slices parked in a per-entry workspace, folded by the table's second launch (one atomic per element)
     ws = torch.empty(lib.rv_gemm_splitk_workspace_bytes(m, n, splitk, batch) // 4, device=c.device, dtype=torch.float32) \
         if (splitk > 1 and _TABLE_PARK) else None
-    rc = lib.rv_gemm_table_fill(tab.host.data_ptr() + tab.n * tab.eb, pa, sam, sak, pb, sbk, sbn, pc, scm, scn, None, m, n, k,
+    rc = lib.rv_gemm_table_fill(tab.slot(), pa, sam, sak, pb, sbk, sbn, pc, scm, scn, None, m, n, k,
                                 splitk, batch, bstrides[0], bstrides[1], bstrides[2], ptr(a_rowsum), ptr(ws))
     if rc < 0:
         raise RuntimeError(f'rv_gemm_table_fill failed ({rc}): {_lib.last_error()}')
@@ -2126,23 +1916,10 @@ THICK_TAPS = 25
 THICK_LINEAR_SPLITK = 48   # fixed (not tuned per M): a frame's logits must not depend on how many frames share the launch (chunked evaluation)
 
 
-def _pack_plain(w, tag, args, numel):
-    """Plain [tap][k][n] re-indexed copy of a weight through the packed-weight cache (part of the PackPlan table)."""
-    key = (w.data_ptr(), 'thick', tag)
-    ver = (_EPOCH[0], w._version, tuple(w.shape))
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    out = torch.empty(numel, device=w.device, dtype=torch.float32)
-    call('rv_pack_weights', ptr(w), ptr(out), *args, stream())
-    _pack_put(key, (ver, out, w, args))
-    return out
-
-
 def thick_wj(w):
     """CNN_time.weight [N, C, 1, 25] -> wj [25][N][C] (tap-major: the forward kernel's and the input-gradient GEMMs' operand)."""
     n, c, _, taps = w.shape
-    return _pack_plain(w, 'wj', (taps, n, c, c * taps, taps, 0, 0, 1), w.numel()).view(taps, n, c)
+    return _pack_plain(w, ('thick', 'wj'), (taps, n, c, c * taps, taps, 0, 0, 1), w.numel()).view(taps, n, c)
 
 
 def thick_feature_index(c, f, channels=4096, rows=THICK_F):
@@ -2154,7 +1931,7 @@ def thick_wlt(w, channels):
     """linear.weight [88, channels*51] in the checkpoint's c*51 + f feature order -> [51*channels, 88]: transposed, z3's f*channels + c order."""
     n, k = w.shape
     rows = k // channels
-    return _pack_plain(w, 'wlt', (rows, channels, n, rows, k, 0, 0, 1), w.numel()).view(k, n)
+    return _pack_plain(w, ('thick', 'wlt'), (rows, channels, n, rows, k, 0, 0, 1), w.numel()).view(k, n)
 
 
 def thick_wlt_grad_to_checkpoint(dwlt, channels):

@@ -93,36 +93,31 @@ def _miss(kind, key):
         print(f'[plans] {kind} shape {key} is not in the shipped table: library default tile', file=sys.stderr)
 
 
-def lookup_conv(key):
-    """(algo, exact) for a conv launch key (mode, B, H, W, cin, cout, ild, old, stats, bnbwd) or None."""
+def _lookup(kind, key):
+    """(value, exact) of the entry for `key`, else of the same geometry at the nearest batch size (key[1]), else None."""
     _load()
     key = tuple(int(x) for x in key)
-    if key in _state['conv']:
-        HITS['conv'].add(key)
-        return _state['conv'][key], True
-    cands = _state['conv_nob'].get((key[0],) + key[2:])
+    if key in _state[kind]:
+        HITS[kind].add(key)
+        return _state[kind][key], True
+    cands = _state[kind + '_nob'].get((key[0],) + key[2:])
     if cands:
-        _, src, algo = _nearest_batch(cands, key[1])
-        HITS['conv'].add(src)
-        return algo, False
-    _miss('conv', key)
+        _, src, value = _nearest_batch(cands, key[1])
+        HITS[kind].add(src)
+        return value, False
+    _miss(kind, key)
     return None
+
+
+def lookup_conv(key):
+    """(algo, exact) for a conv launch key (mode, B, H, W, cin, cout, ild, old, stats, bnbwd) or None."""
+    return _lookup('conv', key)
 
 
 def lookup_wgrad(key):
     """(nw, wgs) for a weight-gradient key (taps, B, Hv, Wv, Ca, Cb) or None."""
-    _load()
-    key = tuple(int(x) for x in key)
-    if key in _state['wgrad']:
-        HITS['wgrad'].add(key)
-        return _state['wgrad'][key]
-    cands = _state['wgrad_nob'].get((key[0],) + key[2:])
-    if cands:
-        _, src, plan = _nearest_batch(cands, key[1])
-        HITS['wgrad'].add(src)
-        return plan
-    _miss('wgrad', key)
-    return None
+    hit = _lookup('wgrad', key)
+    return hit and hit[0]
 
 
 def gemm_entries():

@@ -167,6 +167,60 @@ def test_conv_autotuner(dev, cin, cout, H, W):
     assert rel_err(stats.view(-1, 2 * cout).sum(0), torch.cat([zd.sum(0), (zd * zd).sum(0)])) < 1e-6
 
 
+@pytest.mark.autotune
+def test_online_tuner_offers_the_candidate_lists(dev, monkeypatch):
+    """What the on-line tuner hands the library is tuning.conv_candidates / wgrad_candidates, in order; it keeps a candidate the library accepted,
+    and the second launch of a shape tunes nothing.  (The smallest 3x3 shape that has every candidate family; no timing is asserted.)"""
+    from reconvat_amd import _lib, ops, tuning
+    lib = _lib.load()
+    for name in ('_algo_cache', '_wgrad_tuned', '_wgrad_plans', '_wgrad_owner'):
+        monkeypatch.setattr(tuning, name, type(getattr(tuning, name))())
+    H, W, C = 16, 14, 16
+    x, dy = nhwc(rnd(1, C, H, W, seed=1)).to(dev), nhwc(rnd(1, C, H, W, seed=4)).to(dev)
+    w, b = rnd(C, C, 3, 3, seed=2, scale=0.2).to(dev), rnd(C, seed=3).to(dev)
+    out = torch.empty_like(x)
+    seen, conv_fwd, set_plan, wgrad = [], lib.rv_conv_fwd, lib.rv_conv_wgrad_set_plan, lib.rv_conv_wgrad
+
+    def record(fn, what):
+        def wrapped(*args):
+            rc = fn(*args)
+            seen.append((what(args), rc))
+            return rc
+        return wrapped
+
+    def in_order(items):
+        return list(dict.fromkeys(items))
+    monkeypatch.setattr(lib, 'rv_conv_fwd', record(conv_fwd, lambda a: a[15]))
+    ops.conv_forward_into('c3', x, w, b, out)
+    cands = tuning.conv_candidates(0, H, W, C, C)
+    assert {tuning.decode(c)[0] for c in cands} == {0, *tuning.FAMILIES} - {5, 14}
+    assert in_order(a for a, _ in seen) == cands
+    (key, chosen), = tuning._algo_cache.items()
+    assert key[:6] == (0, 1, H, W, C, C) and (chosen, 0) in seen
+    del seen[:]
+    ops.conv_forward_into('c3', x, w, b, out)
+    assert seen == [(chosen, 0)]                                         # cache hit: the launch itself, nothing else
+    monkeypatch.setattr(lib, 'rv_conv_fwd', conv_fwd)
+
+    del seen[:]
+    monkeypatch.setattr(lib, 'rv_conv_wgrad_set_plan', record(set_plan, lambda a: tuple(a[5:7])))
+    monkeypatch.setattr(lib, 'rv_conv_wgrad', record(wgrad, lambda a: 'launch'))
+    try:
+        ops.conv_wgrad('c3', x, dy, w)
+        plans_seen = [(p, rc) for p, rc in seen if p != 'launch']
+        assert in_order(p for p, _ in plans_seen) == tuning.wgrad_candidates(9, H) and len(tuning.wgrad_candidates(9, H)) == 9
+        chosen = tuning._wgrad_plans[(9, 1, H, W, C, C)]
+        assert seen[-2:] == [(chosen, 0), ('launch', 0)]                 # the winner is pinned, then the launch itself
+        tried = seen[:-2]
+        assert chosen in {p for (p, rc), nxt in zip(tried, tried[1:]) if p != 'launch' and rc == 0 and nxt == ('launch', 0)}
+        del seen[:]
+        ops.conv_wgrad('c3', x, dy, w)
+        assert seen == [('launch', 0)]                                   # tuned: no plan is offered again
+    finally:
+        set_plan(9, 1, H, C, C, 0, 0)                                     # back to the library default partition
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize('cin,cout,H,W,algo', [(16, 16, 21, 37, 0), (32, 24, 9, 57, 0x221), (64, 128, 12, 28, 0x321), (16, 8, 10, 19, 0),
                                                (32, 32, 8, 30, 1), (1, 16, 9, 31, 0), (1, 16, 35, 150, 0), (1, 8, 19, 140, 0), (48, 24, 7, 114, 0x412),
                                                (32, 24, 11, 114, 0x723), (64, 128, 23, 57, 0x713), (8, 16, 12, 229, 0x716), (48, 32, 9, 57, 0x725)])

@@ -3,7 +3,7 @@
 for the library; the shipped plan table decides the plans)."""
 import pytest
 
-from reconvat_amd import ops, plans
+from reconvat_amd import ops, plans, tuning
 
 
 class Lib:
@@ -20,7 +20,9 @@ class Lib:
 def fresh(monkeypatch):
     monkeypatch.setattr(ops, 'AUTOTUNE', 'table')
     for name in ('_wgrad_tuned', '_wgrad_plans', '_wgrad_owner'):
-        monkeypatch.setattr(ops, name, type(getattr(ops, name))())
+        fresh_state = type(getattr(tuning, name))()       # the state lives in tuning; ops re-exports the same objects
+        monkeypatch.setattr(tuning, name, fresh_state)
+        monkeypatch.setattr(ops, name, fresh_state)
     return Lib()
 
 
