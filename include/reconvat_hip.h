@@ -221,6 +221,17 @@ int rv_adam_step(float* p, const float* g, float* m, float* v, long n, const lon
                  float decay_rate, float beta1, float beta2, float eps, float grad_scale, const int* skip, void* stream);
 int rv_counter_add(long* counter, long inc, const int* skip_if_set, void* stream);   /* skip_if_set nullable: no add while *skip != 0 */
 int rv_clip_scale(float* g, long n, const float* total_norm, float max_norm, void* stream);
+/* rv_adam_step with the optimiser options, all in the same pass: g is multiplied by grad_scale and by the clip
+ * coefficient min(1, max_grad_norm / (*total_norm * grad_scale + 1e-6)) -- torch's clip_grad_norm_ BEFORE the step; 1 when
+ * max_grad_norm <= 0 or total_norm is null; *total_norm = rv_reduce_mean(kind 3) of g as stored --, p is multiplied by
+ * 1 - lr * weight_decay before the Adam update (torch.optim.AdamW), and ema (nullable) = ema_decay * ema + (1 - ema_decay) * p.
+ * An element with zero gradient and zero moments keeps its p (torch skips tensors without a gradient; the only deviation: an
+ * element of a touched tensor whose gradient has been exactly zero since step 1 is not decayed).  While *skip != 0 nothing is
+ * written.  weight_decay = 0, max_grad_norm = 0, ema null: bit-identical to rv_adam_step. */
+int rv_adamw_step(float* p, const float* g, float* m, float* v, long n, const long* step, float lr0, long decay_steps,
+                  float decay_rate, float beta1, float beta2, float eps, float grad_scale, const int* skip, float weight_decay,
+                  float max_grad_norm, const float* total_norm, float* ema, float ema_decay, void* stream);
+int rv_swap_floats(float* a, float* b, long n, void* stream);   /* exchange two buffers in place */
 
 /* ---- data feed: PianoRollAudioDataset.__getitem__ (model/dataset.py:35-69) for a whole batch on the device.
  * audio: int16 corpus; label, velocity (nullable): uint8 corpora ([steps, n_keys] rolls, label 3 = onset, 2 = frame,

@@ -9,6 +9,7 @@ MI355X-side additions: one process per GPU under torch.distributed.run (data-par
 gradient all-reduce per step), the fused FlatAdam, optional whole-step hipGraph replay (`graph=True`) and
 `train_on=Synthetic`.
 """
+import contextlib
 import json
 import os
 import time
@@ -26,6 +27,10 @@ ds_ksize, ds_stride = (2, 2), (2, 2)
 mode = 'imagewise'
 logging_freq = 100
 saving_freq = 200
+# optimiser options of the fused step (fused_optimizer=True only), all off by default: decoupled weight decay, an
+# exponential moving average of the weights (checkpointed as model-{ep}.ema.pt, used for every validation), and
+# clip_before_step=True: `clip_gradient_norm` limits the update (the reference clips after the step, which limits nothing)
+OPTIM_OPTIONS = dict(weight_decay=0.0, ema_decay=0.0, clip_before_step=False)
 
 
 def base_config(o, onset_script):
@@ -43,6 +48,7 @@ def base_config(o, onset_script):
         device_metrics=True,   # validation: note decoding, frame counters and AP on the device; False = the host metric code
         tune_thresholds=False,  # True: choose onset / frame threshold on the validation set before the final evaluation
         dtype='fp32',          # 'bf16': opt-in experiment -- bf16-operand backward convs of the final graphs (forward stays fp32)
+        **OPTIM_OPTIONS,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -76,7 +82,7 @@ def baseline_config(o):
         sequence_length=327680, epoches=20000, learning_rate=5e-4, learning_rate_decay_steps=10000,
         learning_rate_decay_rate=0.98, leave_one_out=None, clip_gradient_norm=3, refresh=False, reconstruction=False,
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
-        device_metrics=True, tune_thresholds=False,
+        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS,
     )
     c.update(o)
     if c['model_name'] not in ('onset_frame', 'frame', 'onset'):
@@ -98,7 +104,7 @@ def thickstun_config(o):
         step_size_up=100, max_lr=1e-4, learning_rate=1e-4, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.98,
         leave_one_out=None, clip_gradient_norm=3, refresh=False,
         graph=True, fused_optimizer=True, saving_freq=10, logging_freq=10, device_feed=True,
-        device_metrics=True, tune_thresholds=False,
+        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -160,9 +166,13 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  train_batch_size, learning_rate, learning_rate_decay_steps, learning_rate_decay_rate, alpha,
                  clip_gradient_norm, validation_length, refresh, device, epoches, logdir, log, iteration, VAT_start, VAT,
                  XI, eps, reconstruction, graph, fused_optimizer, saving_freq, device_feed=True, model_complexity=48, model_name='onset_frame', VAT_mode='all',
-                 logging_freq=logging_freq, dtype='fp32', device_metrics=True, tune_thresholds=False, **_unused):
+                 logging_freq=logging_freq, dtype='fp32', device_metrics=True, tune_thresholds=False, weight_decay=0.0, ema_decay=0.0,
+                 clip_before_step=False, **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    if not fused_optimizer and (weight_decay or ema_decay or clip_before_step):
+        raise SystemExit('weight_decay, ema_decay and clip_before_step are options of the fused optimiser step: they need '
+                         'fused_optimizer=True (the torch optimiser path stays the reference loop).')
     if onset_script == 'thickstun':
         VAT = False                                        # train_baseline_Thickstun.py sets the VAT keys and never uses them
     if not str(device).startswith('cuda') or not torch.cuda.is_available():
@@ -222,7 +232,8 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
     if fused_optimizer:
         optimizer = FlatAdam(model.parameters(), lr=learning_rate, step_size=learning_rate_decay_steps,
                              gamma=learning_rate_decay_rate, data_parallel=world > 1,
-                             sync_error_word=bool(getattr(model, 'has_recurrence', False)))
+                             sync_error_word=bool(getattr(model, 'has_recurrence', False)), weight_decay=weight_decay,
+                             max_grad_norm=float(clip_gradient_norm or 0) if clip_before_step else 0.0, ema_decay=ema_decay)
     else:
         optimizer = torch.optim.Adam(model.parameters(), learning_rate)
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=learning_rate_decay_steps, gamma=learning_rate_decay_rate)
@@ -239,6 +250,16 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                       f'lr {optimizer.current_lr():.6e}')
             else:
                 print(f'Resumed from model-{resume_iteration}.pt')
+        if ema_decay:
+            ema_file = os.path.join(logdir, f'model-{resume_iteration}.ema.pt')
+            if os.path.exists(ema_file):
+                optimizer.load_ema(torch.load(ema_file, map_location=device), model)
+                if rank == 0:
+                    print(f'Resumed the averaged weights from model-{resume_iteration}.ema.pt')
+            elif rank == 0:
+                print(f'No model-{resume_iteration}.ema.pt: the average starts from the resumed weights')
+    # validation, threshold tuning and the final evaluation run on the averaged weights when there are any
+    averaged = (lambda: optimizer.ema_weights()) if ema_decay else contextlib.nullcontext
     n_params = sum(p.numel() for p in model.parameters())
     if rank == 0:
         print(f'{cls.__name__}: {n_params} parameters, world size {world}, device {device}')
@@ -282,17 +303,24 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
             # every `logging_freq` epochs (and after the first) note / frame metrics on the validation segments and the eval-mode
             # loss terms over the labelled loader
             if ep % logging_freq == 0 or ep == 1:
-                log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT and ep >= VAT_start, VAT_start,
-                               device_metrics=device_metrics)
+                if ema_decay:
+                    print(f'Validation of epoch {ep} on the averaged weights (ema_decay={ema_decay})')
+                with averaged():
+                    log_validation(model, val_set, l_loader, ep, writer, reconstruction, onset_script, VAT and ep >= VAT_start, VAT_start,
+                                   device_metrics=device_metrics)
             for key, value in losses.items():
                 writer.add_scalar(key, float(value), ep)
             if ep % saving_freq == 0:
                 torch.save(model.state_dict(), os.path.join(logdir, f'model-{ep}.pt'))
+                if ema_decay:
+                    torch.save(optimizer.ema_state_dict(model), os.path.join(logdir, f'model-{ep}.ema.pt'))
                 torch.save(optimizer.state_dict(), os.path.join(logdir, 'last-optimizer-state.pt'))
         if world > 1 and (ep % logging_freq == 0 or ep == 1):
             dp.wait_for_rank0()                            # the other ranks wait for rank 0's validation pass
     if rank == 0:
         torch.save(model.state_dict(), os.path.join(logdir, 'model-final.pt'))
+        if ema_decay:
+            torch.save(optimizer.ema_state_dict(model), os.path.join(logdir, 'model-final.ema.pt'))
         # final evaluation exactly as the reference scripts end (train_UNet_Onset_VAT.py:156-170): WHOLE songs of the test split
         # (`full_validation`, sequence_length=None), transcriptions written to <logdir>/MIDI_results, metrics pickled to
         # <logdir>/result_dict
@@ -301,18 +329,21 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         print('Training finished, now evaluating on the test split (full songs)')
         model.eval()
         chosen = {}
-        if tune_thresholds:
-            # thresholds chosen on the validation split, the test songs then evaluated at the chosen pair
-            from .evaluate import tune_thresholds as sweep_validation
-            grid = [round(0.1 * k, 1) for k in range(1, 10)]
+        if ema_decay:
+            print(f'Threshold tuning and the final evaluation run on the averaged weights (ema_decay={ema_decay})')
+        with averaged():
+            if tune_thresholds:
+                # thresholds chosen on the validation split, the test songs then evaluated at the chosen pair
+                from .evaluate import tune_thresholds as sweep_validation
+                grid = [round(0.1 * k, 1) for k in range(1, 10)]
+                with torch.no_grad():
+                    tuned = sweep_validation(val_set, model, grid, grid, device_metrics=device_metrics)
+                chosen = {'onset_threshold': tuned['onset_threshold'], 'frame_threshold': tuned['frame_threshold']}
+                print(f"Thresholds chosen on {tuned['songs']} validation items: onset {chosen['onset_threshold']:.2f}, frame "
+                      f"{chosen['frame_threshold']:.2f} (mean note F1 {tuned['best_value']:.4f})")
             with torch.no_grad():
-                tuned = sweep_validation(val_set, model, grid, grid, device_metrics=device_metrics)
-            chosen = {'onset_threshold': tuned['onset_threshold'], 'frame_threshold': tuned['frame_threshold']}
-            print(f"Thresholds chosen on {tuned['songs']} validation items: onset {chosen['onset_threshold']:.2f}, frame "
-                  f"{chosen['frame_threshold']:.2f} (mean note F1 {tuned['best_value']:.4f})")
-        with torch.no_grad():
-            metrics = evaluate_wo_velocity(full_validation, model, reconstruction=False, save_path=os.path.join(logdir, 'MIDI_results'),
-                                           device_metrics=device_metrics, **chosen)
+                metrics = evaluate_wo_velocity(full_validation, model, reconstruction=False, save_path=os.path.join(logdir, 'MIDI_results'),
+                                               device_metrics=device_metrics, **chosen)
         for key, values in metrics.items():
             if key.startswith('metric/'):
                 _, category, name = key.split('/')

@@ -245,6 +245,117 @@ __global__ __launch_bounds__(256) void scale_by_clip_k(float* g, long n, const f
 
 static int grid_for(long n) { long b = (n + 255) / 256; return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096); }
 
+// ---------------------------------------------------------------------------------------------
+// AdamW + StepLR with the optimiser options: clip_grad_norm_ BEFORE the update, decoupled weight decay, an exponential
+// moving average of the weights -- all in the one pass over the flat bucket.  adam_k above is the default path and stays as it is.
+// ---------------------------------------------------------------------------------------------
+struct AdamWArgs {
+    AdamArgs a;
+    float weight_decay, max_grad_norm;
+    const float* total_norm;   // nullable: L2 norm of the bucket as stored (before grad_scale)
+    float* ema;                // nullable
+    float ema_decay;
+    long i0;                   // scalar kernel: first element
+};
+
+struct AdamWCoef { float gmul, step_size, bc2s, keep; };
+
+// lr / bc1 / bc2s / step_size: adam_k's expressions, character for character
+__device__ __forceinline__ AdamWCoef adamw_coef(const AdamWArgs& w) {
+#pragma clang fp contract(off)
+    const AdamArgs& a = w.a;
+    const long step = *a.step;
+    const double t = (double)(step + 1);
+    const float lr = a.lr0 * (float)pow((double)a.decay_rate, (double)(step / a.decay_steps));
+    const float bc1 = (float)(1.0 - pow((double)a.b1, t));
+    const float bc2s = (float)sqrt(1.0 - pow((double)a.b2, t));
+    AdamWCoef c;
+    c.step_size = lr / bc1;
+    c.bc2s = bc2s;
+    // torch.nn.utils.clip_grad_norm_ on the SCALED gradient: coef = clamp(max_norm / (total_norm + 1e-6), max=1)
+    c.gmul = 1.f;
+    if (w.max_grad_norm > 0.f && w.total_norm) c.gmul = fminf(w.max_grad_norm / (*w.total_norm * a.grad_scale + 1e-6f), 1.f);
+    c.keep = 1.f - lr * w.weight_decay;
+    return c;
+}
+
+// One element.  Contraction is OFF and the two fused multiply-adds are the ones the compiler forms in adam_k (v, and the update of
+// p): with weight_decay = 0, max_grad_norm = 0 the only extra operations are g * 1.f and p * 1.f, so p, m, v equal adam_k's bit for
+// bit (tests/test_optim_options_gpu.py holds the two kernels against each other).
+// Element rule: g == 0 with zero moments keeps p (no decay) -- torch skips tensors whose .grad is None, and the pad elements and
+// never-touched tensors of the flat bucket are exactly these elements.  It deviates from torch.optim.AdamW only for an element of a
+// TOUCHED tensor whose gradient has been exactly zero since step 1: torch decays it, this kernel does not.
+__device__ __forceinline__ void adamw_elem(const AdamWArgs& w, const AdamWCoef& c, float graw, float& p, float& m, float& v, float& e) {
+#pragma clang fp contract(off)
+    const AdamArgs& a = w.a;
+    const float g = graw * a.grad_scale * c.gmul;
+    const bool idle = g == 0.f && m == 0.f && v == 0.f;
+    m = m * a.b1 + (1.f - a.b1) * g;
+    v = __builtin_fmaf((1.f - a.b2) * g, g, v * a.b2);
+    if (!idle) {
+        const float denom = sqrtf(v) / c.bc2s + a.eps;
+        p = __builtin_fmaf(-c.step_size, m / denom, p * c.keep);
+    }
+    if (w.ema) e = w.ema_decay * e + (1.f - w.ema_decay) * p;
+}
+
+// n % 4 == 0 and 16-byte bases (what FlatAdam always has): dwordx4 loads and stores, up to six streams, grid-stride
+__global__ __launch_bounds__(256) void adamw_vec_k(AdamWArgs w) {
+    const AdamArgs& a = w.a;
+    if (a.skip && *a.skip != 0) return;
+    const AdamWCoef c = adamw_coef(w);
+    const long n4 = a.n >> 2;
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(a.g);
+    f32x4* p4 = reinterpret_cast<f32x4*>(a.p);
+    f32x4* m4 = reinterpret_cast<f32x4*>(a.m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(a.v);
+    f32x4* e4 = reinterpret_cast<f32x4*>(w.ema);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 g = g4[i];
+        f32x4 p = p4[i], m = m4[i], v = v4[i];
+        f32x4 e = e4 ? e4[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float pq = p[q], mq = m[q], vq = v[q], eq = e[q];
+            adamw_elem(w, c, g[q], pq, mq, vq, eq);
+            p[q] = pq; m[q] = mq; v[q] = vq; e[q] = eq;
+        }
+        m4[i] = m; v4[i] = v; p4[i] = p;
+        if (e4) e4[i] = e;
+    }
+}
+
+// any n / alignment (C-ABI callers), and the n % 4 tail of the vector kernel: elements [i0, n)
+__global__ __launch_bounds__(256) void adamw_k(AdamWArgs w) {
+    const AdamArgs& a = w.a;
+    if (a.skip && *a.skip != 0) return;
+    const AdamWCoef c = adamw_coef(w);
+    for (long i = w.i0 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        float p = a.p[i], m = a.m[i], v = a.v[i], e = w.ema ? w.ema[i] : 0.f;
+        adamw_elem(w, c, a.g[i], p, m, v, e);
+        a.m[i] = m; a.v[i] = v; a.p[i] = p;
+        if (w.ema) w.ema[i] = e;
+    }
+}
+
+__global__ __launch_bounds__(256) void swap_vec_k(f32x4* a, f32x4* b, long n4) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+__global__ __launch_bounds__(256) void swap_k(float* a, float* b, long i0, long n) {
+    for (long i = i0 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// vector kernels: one 16-byte quad per thread and pass, at most 8 workgroups of 256 per CU
+static int grid_for_quads(long n4) { long b = (n4 + 255) / 256; return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048); }
+
 extern "C" {
 
 // x_adv = clamp(x + scale*normalise_rows(prescale*d), 0, 1); optional r (=scale*dn) and dn outputs;
@@ -420,6 +531,49 @@ int rv_counter_add(long* counter, long inc, const int* skip, void* stream) {
 int rv_clip_scale(float* g, long n, const float* total_norm, float max_norm, void* stream) {
     hipLaunchKernelGGL(scale_by_clip_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, n, total_norm, max_norm);
     RV_LAUNCH_CHECK("rv_clip_scale");
+    return RV_OK;
+}
+
+// rv_adam_step with the optimiser options (see adamw_elem for the per-element semantics): g is scaled by grad_scale and by the
+// clip coefficient min(1, max_grad_norm / (*total_norm * grad_scale + 1e-6)) (1 when max_grad_norm <= 0 or total_norm is null;
+// *total_norm = L2 norm of g as stored, rv_reduce_mean kind 3), p is decayed by 1 - lr * weight_decay before the Adam update, and
+// ema (nullable) becomes ema_decay * ema + (1 - ema_decay) * p.  While *skip != 0 nothing is written, ema included.  With
+// weight_decay = 0, max_grad_norm = 0 and ema null the result equals rv_adam_step's bit for bit.  n % 4 == 0 with 16-byte aligned
+// buffers takes 16-byte loads and stores; anything else a scalar kernel.
+int rv_adamw_step(float* p, const float* g, float* m, float* v, long n, const long* step, float lr0, long decay_steps,
+                  float decay_rate, float beta1, float beta2, float eps, float grad_scale, const int* skip, float weight_decay,
+                  float max_grad_norm, const float* total_norm, float* ema, float ema_decay, void* stream) {
+    RV_CHECK_ARG(p && g && m && v && step && n >= 0 && decay_steps > 0, "rv_adamw_step: null buffer, negative n or decay_steps <= 0");
+    RV_CHECK_ARG(weight_decay >= 0.f && ema_decay >= 0.f && ema_decay < 1.f, "rv_adamw_step: weight_decay < 0 or ema_decay outside [0, 1)");
+    if (n == 0) return RV_OK;
+    AdamWArgs w;
+    AdamArgs& a = w.a;
+    a.skip = skip;
+    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.step = step; a.lr0 = lr0; a.decay_steps = decay_steps;
+    a.decay_rate = decay_rate; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.grad_scale = grad_scale;
+    w.weight_decay = weight_decay; w.max_grad_norm = max_grad_norm; w.total_norm = total_norm; w.ema = ema; w.ema_decay = ema_decay;
+    w.i0 = 0;
+    const bool vec = n >= 4 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(ema);
+    if (vec) {
+        hipLaunchKernelGGL(adamw_vec_k, dim3(grid_for_quads(n >> 2)), dim3(256), 0, (hipStream_t)stream, w);
+        w.i0 = n & ~3L;
+    }
+    if (w.i0 < n) hipLaunchKernelGGL(adamw_k, dim3(grid_for(n - w.i0)), dim3(256), 0, (hipStream_t)stream, w);
+    RV_LAUNCH_CHECK("rv_adamw_step");
+    return RV_OK;
+}
+
+// a <-> b in place (FlatAdam.ema_weights: the averaged weights take the place of the raw ones and back)
+int rv_swap_floats(float* a, float* b, long n, void* stream) {
+    RV_CHECK_ARG(a && b && n >= 0, "rv_swap_floats: null buffer or negative n");
+    if (n == 0 || a == b) return RV_OK;
+    long i0 = 0;
+    if (n >= 4 && aligned16(a) && aligned16(b)) {
+        hipLaunchKernelGGL(swap_vec_k, dim3(grid_for_quads(n >> 2)), dim3(256), 0, (hipStream_t)stream, (f32x4*)a, (f32x4*)b, n >> 2);
+        i0 = n & ~3L;
+    }
+    if (i0 < n) hipLaunchKernelGGL(swap_k, dim3(grid_for(n - i0)), dim3(256), 0, (hipStream_t)stream, a, b, i0, n);
+    RV_LAUNCH_CHECK("rv_swap_floats");
     return RV_OK;
 }
 

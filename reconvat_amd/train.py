@@ -74,7 +74,8 @@ def train_VAT_model(model, iteration, ep, l_loader, ul_loader, optimizer, schedu
         if clip_gradient_norm:
             # the reference clips AFTER the step (no effect on the update); kept for .grad parity
             if isinstance(optimizer, FlatAdam):
-                optimizer.clip_grad_norm_(clip_gradient_norm)
+                if not optimizer.max_grad_norm:            # (max_grad_norm: the step has already used the gradient clipped)
+                    optimizer.clip_grad_norm_(clip_gradient_norm)
             else:
                 torch.nn.utils.clip_grad_norm_(model.parameters(), clip_gradient_norm)
         print(f'Train Epoch: {ep} [{i * batch_size}/{iteration * batch_size}'
@@ -106,7 +107,8 @@ def train_model(model, ep, loader, optimizer, scheduler, clip_gradient_norm):
         if clip_gradient_norm:
             # the reference clips AFTER the step (no effect on the update); kept for .grad parity
             if isinstance(optimizer, FlatAdam):
-                optimizer.clip_grad_norm_(clip_gradient_norm)
+                if not optimizer.max_grad_norm:            # (max_grad_norm: the step has already used the gradient clipped)
+                    optimizer.clip_grad_norm_(clip_gradient_norm)
             else:
                 torch.nn.utils.clip_grad_norm_(model.parameters(), clip_gradient_norm)
         batch_idx += 1
@@ -141,10 +143,22 @@ class FlatAdam:
     Parameters are re-pointed to views of ``flat_param`` and their ``.grad`` to views of ``flat_grad``,
     so autograd accumulates straight into the bucket that data-parallel training all-reduces.
     Parameters that never receive a gradient keep a zero gradient and zero moments -> they do not move,
-    which is what torch.optim.Adam does by skipping them (6 such tensors in UNet_Onset)."""
+    which is what torch.optim.Adam does by skipping them (6 such tensors in UNet_Onset).
+
+    Optimiser options, all off by default and then `step()` is the plain Adam kernel:
+    ``weight_decay`` -- decoupled decay, torch.optim.AdamW's `p *= 1 - lr * weight_decay` before the update;
+    ``max_grad_norm`` -- torch's `clip_grad_norm_` applied BEFORE the update (the norm of the all-reduced bucket is reduced on the
+    device and the coefficient applied inside the kernel; the stored gradient is left unclipped);
+    ``ema_decay`` -- `flat_ema = d * flat_ema + (1 - d) * flat_param` after every applied step, see `ema_weights()`.
+    Elements with a zero gradient and zero moments (never-touched tensors, pad elements) are neither decayed nor moved."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, step_size=1000, gamma=0.98, data_parallel=None,
-                 sync_error_word=False):
+                 sync_error_word=False, weight_decay=0.0, max_grad_norm=0.0, ema_decay=0.0):
+        weight_decay, max_grad_norm, ema_decay = float(weight_decay), float(max_grad_norm), float(ema_decay)
+        if weight_decay < 0 or max_grad_norm < 0 or ema_decay < 0:
+            raise ValueError(f'weight_decay={weight_decay}, max_grad_norm={max_grad_norm}, ema_decay={ema_decay}: none may be negative')
+        if ema_decay >= 1:
+            raise ValueError(f'ema_decay={ema_decay}: must be below 1 (0 switches the average off)')
         self.params = [p for p in params if p.requires_grad]
         assert self.params, 'no trainable parameters'
         dev = self.params[0].device
@@ -171,6 +185,13 @@ class FlatAdam:
             p.grad = self.flat_grad[off:off + k].view_as(p.data)
         self.n = n
         self.lr, self.betas, self.eps, self.step_size, self.gamma = lr, betas, eps, step_size, gamma
+        self.weight_decay, self.max_grad_norm, self.ema_decay = weight_decay, max_grad_norm, ema_decay
+        # workspace of the gradient-norm reduction: allocated once (not per call as in clip_grad_norm_) so that step() can sit
+        # inside a captured graph
+        self.norm_ws = torch.empty((n + 2047) // 2048, device=dev, dtype=torch.float32) if max_grad_norm > 0 else None
+        # the averaged weights start as a COPY of the weights (no bias correction needed)
+        self.flat_ema = self.flat_param.clone() if ema_decay > 0 else None
+        self._ema_swapped = False
         self.grad_scale = 1.0
         ops.step_error_word(dev)                # create the per-device error word outside any graph capture
         # the ONE all-reduce call site of a step is step(); None = whenever a process group with world > 1 is up
@@ -213,11 +234,22 @@ class FlatAdam:
                 p.grad = self.flat_grad[off:off + p.numel()].view_as(p.data)
 
     def step(self):
+        if self._ema_swapped:
+            raise RuntimeError('FlatAdam.step() inside ema_weights(): the averaged weights are in place of the raw ones')
         if self.data_parallel or self.data_parallel is None:
             allreduce_gradients(self)              # the ONE collective of a step (no-op without a process group)
-        call('rv_adam_step', ptr(self.flat_param), ptr(self.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
-             ptr(self.step_count), self.lr, self.step_size, self.gamma, self.betas[0], self.betas[1], self.eps,
-             self.grad_scale, ptr(ops.step_error_word(self.flat_grad.device)), stream())
+        if not (self.weight_decay or self.max_grad_norm or self.ema_decay):
+            call('rv_adam_step', ptr(self.flat_param), ptr(self.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
+                 ptr(self.step_count), self.lr, self.step_size, self.gamma, self.betas[0], self.betas[1], self.eps,
+                 self.grad_scale, ptr(ops.step_error_word(self.flat_grad.device)), stream())
+        else:
+            if self.max_grad_norm > 0:
+                # L2 norm of the bucket as stored (the all-reduced SUM, side-stream twins merged); the kernel applies grad_scale
+                call('rv_reduce_mean', 3, ptr(self.flat_grad), None, self.n, ptr(self.norm_buf), ptr(self.norm_ws), None, stream())
+            call('rv_adamw_step', ptr(self.flat_param), ptr(self.flat_grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
+                 ptr(self.step_count), self.lr, self.step_size, self.gamma, self.betas[0], self.betas[1], self.eps,
+                 self.grad_scale, ptr(ops.step_error_word(self.flat_grad.device)), self.weight_decay, self.max_grad_norm,
+                 ptr(self.norm_buf) if self.max_grad_norm > 0 else None, ptr(self.flat_ema), self.ema_decay, stream())
         # (same skip word: a step whose update was skipped advances neither StepLR nor the bias correction -- `step_count`, and with
         # it the `step` of state_dict(), counts APPLIED updates, not calls; the word stays set until check() reports it, so every
         # step between a fault and the next check() is skipped on all ranks alike)
@@ -233,6 +265,61 @@ class FlatAdam:
     def current_lr(self):
         return self.lr * self.gamma ** (int(self.step_count.item()) // self.step_size)
 
+    def _require_ema(self):
+        if self.flat_ema is None:
+            raise RuntimeError('this FlatAdam keeps no averaged weights (ema_decay=0)')
+
+    def _swap_ema(self):
+        call('rv_swap_floats', ptr(self.flat_param), ptr(self.flat_ema), self.n, stream())
+        ops.invalidate_weight_cache()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters ARE the averaged weights (flat_param and flat_ema exchanged in place, packed
+        weights invalidated); on exit the raw weights are back, bit for bit.  BatchNorm running statistics are buffers, not
+        parameters: the averaged model uses the live ones.  Not while a stream is capturing, and no step() inside."""
+        self._require_ema()
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ema_weights() cannot run while a stream is capturing')
+        if self._ema_swapped:
+            raise RuntimeError('ema_weights() is not re-entrant')
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
+    def ema_state_dict(self, model):
+        """`model.state_dict()` (same keys, same order) with every parameter this optimiser trains taken from the averaged
+        weights; buffers -- BatchNorm running statistics included -- are the live ones.  An ordinary checkpoint."""
+        self._require_ema()
+        src = self.flat_param if self._ema_swapped else self.flat_ema     # inside ema_weights() the buffers are exchanged
+        sd = model.state_dict()
+        slot = {id(p): (p, off) for p, off in zip(self.params, self.offsets)}
+        for name, p in model.named_parameters():
+            if id(p) in slot and name in sd:
+                q, off = slot[id(p)]
+                sd[name] = src[off:off + q.numel()].view_as(q).clone()
+        return sd
+
+    def load_ema(self, state_dict, model):
+        """Fill the averaged weights from an `ema_state_dict()` of `model` (entries of parameters only; buffers are ignored)."""
+        self._require_ema()
+        dst = self.flat_param if self._ema_swapped else self.flat_ema
+        slot = {id(p): (p, off) for p, off in zip(self.params, self.offsets)}
+        for name, p in model.named_parameters():
+            if id(p) not in slot:
+                continue
+            if name not in state_dict:
+                raise KeyError(f'averaged weights: {name} is missing')
+            q, off = slot[id(p)]
+            t = state_dict[name]
+            if tuple(t.shape) != tuple(q.shape):
+                raise ValueError(f'averaged weights {name}: shape {tuple(t.shape)} vs parameter {tuple(q.shape)}')
+            dst[off:off + q.numel()].copy_(t.reshape(-1))
+
     def state_dict(self):
         """The `torch.optim.Adam.state_dict()` layout (what the reference writes to last-optimizer-state.pt,
         train_UNet_Onset_VAT.py:152): per-parameter `step` / `exp_avg` / `exp_avg_sq` keyed by parameter index, plus one
@@ -246,7 +333,7 @@ class FlatAdam:
                 k = p.numel()
                 state[i] = {'step': torch.tensor(float(steps)), 'exp_avg': self.exp_avg[off:off + k].view_as(p).clone(),
                             'exp_avg_sq': self.exp_avg_sq[off:off + k].view_as(p).clone()}
-        group = {'lr': self.current_lr(), 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
+        group = {'lr': self.current_lr(), 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay or 0, 'amsgrad': False,
                  'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
                  'initial_lr': self.lr, 'params': list(range(len(self.params)))}
         return {'state': state, 'param_groups': [group]}
@@ -274,6 +361,7 @@ class FlatAdam:
         g0 = groups[0]
         self.lr = float(g0.get('initial_lr', g0['lr']))
         self.betas, self.eps = tuple(g0['betas']), float(g0['eps'])
+        # (weight_decay of the file is NOT taken over: like max_grad_norm and ema_decay it is what the constructor was given)
 
 
 def allreduce_gradients(opt):
@@ -463,7 +551,7 @@ class TrainStep:
                 self.pack_plan = ops.PackPlan(self.opt.flat_grad.device)
             self._dual_ready = True
         self.opt.step()                        # [RCCL all-reduce of the flat bucket] + Adam + StepLR
-        if self.clip:
+        if self.clip and not self.opt.max_grad_norm:   # (max_grad_norm: the step has already used the gradient clipped)
             self.opt.clip_grad_norm_(self.clip)
         self.pack_plan.run()                   # the next step's forward finds every packed weight fresh
         return self.loss

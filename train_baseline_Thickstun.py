@@ -17,5 +17,6 @@ def config(overrides):
 def train(spec, resume_iteration, train_on, batch_size, sequence_length, small, supersmall, train_batch_size, learning_rate,
           learning_rate_decay_steps, learning_rate_decay_rate, alpha, clip_gradient_norm, validation_length, refresh, device,
           epoches, logdir, log, iteration, VAT_start, VAT, XI, eps, reconstruction, graph, fused_optimizer, saving_freq,
-          device_feed, logging_freq, device_metrics, tune_thresholds):
+          device_feed, logging_freq, device_metrics, tune_thresholds, weight_decay,
+          ema_decay, clip_before_step):
     return run_training('thickstun', **locals())
