@@ -242,6 +242,21 @@ int rv_crop_segments(const short* audio, const unsigned char* label, const unsig
                      const long* label_begin, int B, long seq_len, int n_steps, int n_keys, float* out_audio, float* onset,
                      float* offset, float* frame, float* out_velocity, void* stream);
 
+/* Pitch-shift augmentation of the feed: rv_crop_segments with item b transposed by k_b semitones -- the audio resampled
+ * by the polyphase definition of rv_resample (y[m] = sum_n x[a0 + n] 2^-15 h[m M - n L] over the samples of the item's TRACK, zero
+ * beyond its two ends), the labels moved k keys and rescaled in time in integer arithmetic (reconvat_amd/augment.py has the rule).
+ * audio [n_audio] int16, label / velocity [n_label] uint8; banks [n_bank] float32, 16-byte aligned: the banks [L, Kp] of every shift
+ * (layout of rv_resample), concatenated at multiples of 4 floats; items: DEVICE array [B, 12] of longs per item: a0, t_begin, t_end
+ * (corpus indices of the crop's first sample and of the track's first / one-past-last sample), L, M, F, Kp, bank offset in floats,
+ * byte offset of the crop's first row in the label corpora, source rows that exist from there, k, 0.  L, M <= 128 within a factor
+ * of 2 of each other, Kp <= 256; a row outside these limits yields NaN outputs for its item (never an out-of-range access).
+ * Outputs as rv_crop_segments, none nullable, 16-byte aligned; n_keys a multiple of 4.  A k = 0 item with the bank [1, 0, 0, 0]
+ * (L = M = 1, F = 0, Kp = 4) equals rv_crop_segments bit for bit.  Two launches, no atomics, allocation or synchronisation; every
+ * output is one accumulator summed in a fixed order, so its bits do not depend on B or on the item's place in the batch. */
+int rv_crop_segments_shift(const short* audio, long n_audio, const unsigned char* label, const unsigned char* velocity, long n_label,
+                           const float* banks, long n_bank, const long* items, int B, long seq_len, int n_steps, int n_keys,
+                           float* out_audio, float* onset, float* offset, float* frame, float* out_velocity, void* stream);
+
 /* ---- audio ingest: rational-ratio polyphase FIR resampling with the channel downmix fused in.
  *   y[m] = sum_n x[n] h[m M - n L],  x[n] = mean over the C channels of input frame n (zero outside the signal), L/M = sr_out/sr_in
  * x: [T_in, C] interleaved frames, in_dtype 0 = int16 (scale 2^-15), 1 = int32 (2^-31), 2 = float32; it is the slice

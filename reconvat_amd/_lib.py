@@ -72,6 +72,7 @@ SIGNATURES = {
     'rv_adamw_step': (I, [P, P, P, P, L, P, F, L, F, F, F, F, F, P, F, F, P, P, F, P]),
     'rv_swap_floats': (I, [P, P, L, P]),
     'rv_crop_segments': (I, [P, P, P, P, P, I, L, I, I, P, P, P, P, P, P]),
+    'rv_crop_segments_shift': (I, [P, L, P, P, L, P, L, P, I, L, I, I, P, P, P, P, P, P]),
     'rv_resample_max_coeffs': (L, []),
     'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
     'rv_eval_workspace_bytes': (L, [L]),

@@ -31,6 +31,9 @@ saving_freq = 200
 # exponential moving average of the weights (checkpointed as model-{ep}.ema.pt, used for every validation), and
 # clip_before_step=True: `clip_gradient_norm` limits the update (the reference clips after the step, which limits nothing)
 OPTIM_OPTIONS = dict(weight_decay=0.0, ema_decay=0.0, clip_before_step=False)
+# augmentation of the device feed (device_feed=True only), off by default: every training item -- labelled and
+# unlabelled -- is transposed by a random whole number of semitones in [-pitch_shift, pitch_shift] (at most 6) while it is cropped
+FEED_OPTIONS = dict(pitch_shift=0)
 
 
 def base_config(o, onset_script):
@@ -48,7 +51,7 @@ def base_config(o, onset_script):
         device_metrics=True,   # validation: note decoding, frame counters and AP on the device; False = the host metric code
         tune_thresholds=False,  # True: choose onset / frame threshold on the validation set before the final evaluation
         dtype='fp32',          # 'bf16': opt-in experiment -- bf16-operand backward convs of the final graphs (forward stays fp32)
-        **OPTIM_OPTIONS,
+        **OPTIM_OPTIONS, **FEED_OPTIONS,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -82,7 +85,7 @@ def baseline_config(o):
         sequence_length=327680, epoches=20000, learning_rate=5e-4, learning_rate_decay_steps=10000,
         learning_rate_decay_rate=0.98, leave_one_out=None, clip_gradient_norm=3, refresh=False, reconstruction=False,
         graph=True, fused_optimizer=True, saving_freq=saving_freq, logging_freq=logging_freq, device_feed=True,
-        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS,
+        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS, **FEED_OPTIONS,
     )
     c.update(o)
     if c['model_name'] not in ('onset_frame', 'frame', 'onset'):
@@ -104,7 +107,7 @@ def thickstun_config(o):
         step_size_up=100, max_lr=1e-4, learning_rate=1e-4, learning_rate_decay_steps=1000, learning_rate_decay_rate=0.98,
         leave_one_out=None, clip_gradient_norm=3, refresh=False,
         graph=True, fused_optimizer=True, saving_freq=10, logging_freq=10, device_feed=True,
-        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS,
+        device_metrics=True, tune_thresholds=False, **OPTIM_OPTIONS, **FEED_OPTIONS,
     )
     c.update(o)
     if torch.cuda.is_available() and torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory < 10e9:
@@ -167,12 +170,21 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  clip_gradient_norm, validation_length, refresh, device, epoches, logdir, log, iteration, VAT_start, VAT,
                  XI, eps, reconstruction, graph, fused_optimizer, saving_freq, device_feed=True, model_complexity=48, model_name='onset_frame', VAT_mode='all',
                  logging_freq=logging_freq, dtype='fp32', device_metrics=True, tune_thresholds=False, weight_decay=0.0, ema_decay=0.0,
-                 clip_before_step=False, **_unused):
+                 clip_before_step=False, pitch_shift=0, **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if not fused_optimizer and (weight_decay or ema_decay or clip_before_step):
         raise SystemExit('weight_decay, ema_decay and clip_before_step are options of the fused optimiser step: they need '
                          'fused_optimizer=True (the torch optimiser path stays the reference loop).')
+    if pitch_shift:
+        from .augment import check_shift
+        try:
+            check_shift(pitch_shift)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if not device_feed or not str(device).startswith('cuda'):
+            raise SystemExit('pitch_shift is an option of the device feed (the batch is resampled while it is cropped in HBM): it needs '
+                             'device_feed=True and device=cuda:N (the host DataLoader path stays the reference loop).')
     if onset_script == 'thickstun':
         VAT = False                                        # train_baseline_Thickstun.py sets the VAT keys and never uses them
     if not str(device).startswith('cuda') or not torch.cuda.is_available():
@@ -193,11 +205,16 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                                                         refresh=refresh, device=device, small=small, supersmall=supersmall,
                                                         dataset=train_on, rank=rank)
     if device_feed and hasattr(l_set, 'data') and str(device).startswith('cuda'):
-        # corpus resident in HBM, batches cropped/decoded by rv_crop_segments (reconvat_amd/feed.py)
+        # corpus resident in HBM, batches cropped/decoded by rv_crop_segments (reconvat_amd/feed.py); the training loaders alone
+        # are augmented: validation, test and threshold-tuning sets never are
         from .feed import device_loader
-        l_loader = device_loader(l_set, train_batch_size, device, rank=rank, world=world, seed=42 + rank)
-        ul_loader = device_loader(ul_set, batch_size, device, rank=rank, world=world, seed=43 + rank) if VAT else None
+        l_loader = device_loader(l_set, train_batch_size, device, rank=rank, world=world, seed=42 + rank, pitch_shift=pitch_shift)
+        ul_loader = device_loader(ul_set, batch_size, device, rank=rank, world=world, seed=43 + rank, pitch_shift=pitch_shift) if VAT else None
+        if pitch_shift and rank == 0:
+            print(f'Pitch-shift augmentation: every training item transposed by a random k in [-{pitch_shift}, {pitch_shift}] semitones')
     else:
+        if pitch_shift:
+            raise SystemExit(f'pitch_shift needs the device feed, and the {train_on} training set has no in-memory tracks to keep in HBM.')
         ul_loader = DataLoader(ul_set, batch_size, shuffle=True, drop_last=True) if VAT else None
         l_loader = DataLoader(l_set, train_batch_size, shuffle=True, drop_last=True)
 

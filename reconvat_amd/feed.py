@@ -10,12 +10,18 @@ reproduces ``DataLoader(dataset, batch_size, shuffle=True, drop_last=True)`` + `
   * with ``world > 1`` rank r keeps tracks r, r + world, ... (per-rank shard, disjoint data on every GPU).
 A 8 x 327 680-sample batch is 5 MB of int16 in, 10 MB of fp32 + 9 MB of label masks out: ~10 us of HBM streaming.
 There is no CPU fallback: the corpus tensors must live on a HIP device.
+
+``pitch_shift=p`` (off by default; DESIGN 3.12, reconvat_amd/augment.py) makes every item a copy of its crop transposed by a random
+whole number of semitones in [-p, p]: ``rv_crop_segments_shift`` resamples the audio while it crops and moves the labels along.
 """
 import numpy as np
 import torch
 
+from . import augment
 from .constants import HOP_LENGTH
 from ._lib import call, ptr, stream, need_gpu
+
+ITEM_FIELDS = 12          # longs per item of rv_crop_segments_shift's table (RV_SHIFT_FIELDS in csrc/data.hip)
 
 
 def _pad_to(n, m):
@@ -23,8 +29,10 @@ def _pad_to(n, m):
 
 
 class DeviceCorpus:
-    def __init__(self, tracks, sequence_length, batch_size, device, seed=42, rank=0, world=1, sampler_seed=0):
+    def __init__(self, tracks, sequence_length, batch_size, device, seed=42, rank=0, world=1, sampler_seed=0, pitch_shift=0,
+                 aug_seed=0):
         tracks = list(tracks)[rank::world]
+        self.pitch_shift = augment.check_shift(pitch_shift)
         if not tracks:
             raise ValueError('DeviceCorpus: no tracks for this rank')
         self.sequence_length = int(sequence_length)
@@ -41,6 +49,11 @@ class DeviceCorpus:
                              f'{self.batch_size}; lower the batch size or the number of ranks')
         if (self.lengths <= self.sequence_length).any():
             raise ValueError('every track must be longer than sequence_length (the reference draws randint(T - L))')
+        if self.pitch_shift:
+            widest = augment.span(self.pitch_shift, self.sequence_length)
+            if (self.lengths <= widest).any():
+                raise ValueError(f'pitch_shift={self.pitch_shift}: every track must be longer than the {widest} samples a crop shifted up '
+                                 f'by {self.pitch_shift} semitones reads (the shortest has {int(self.lengths.min())})')
         # concatenate; track starts padded to 8 samples / 16 label bytes so that aligned crops use 16-byte accesses
         a_off, l_off, na, nl = [], [], 0, 0
         for t in tracks:
@@ -66,45 +79,107 @@ class DeviceCorpus:
         self.sampler = torch.Generator().manual_seed(sampler_seed)  # item order (RandomSampler analogue)
         # crop offsets travel through a ring of pinned staging buffers, each guarded by the event of its last upload:
         # a batch drawn while an earlier upload is still queued never overwrites offsets the device has not read yet
-        self._ring = [torch.empty((2, self.batch_size), dtype=torch.int64).pin_memory() for _ in range(4)]
+        # (with pitch_shift the ring carries the per-item table of rv_crop_segments_shift instead)
+        ring_shape = (self.batch_size, ITEM_FIELDS) if self.pitch_shift else (2, self.batch_size)
+        self._ring = [torch.empty(ring_shape, dtype=torch.int64).pin_memory() for _ in range(4)]
         self._ring_events = [None] * len(self._ring)
         self._ring_pos = 0
+        if self.pitch_shift:
+            # a second stream for the shifts, and the 13 polyphase banks, concatenated (each starts at a multiple of 4 floats)
+            self.aug = np.random.RandomState(aug_seed)
+            self.n_rows = np.array([t['label'].shape[0] for t in tracks], dtype=np.int64)
+            self._banks, parts, at = {}, [], 0
+            for k in range(-augment.MAX_SHIFT, augment.MAX_SHIFT + 1):
+                L, M, F, Kp, bank = augment.bank32(k)
+                self._banks[k] = (L, M, F, Kp, at)
+                parts.append(bank.reshape(-1))
+                at += bank.size                                    # Kp is a multiple of 4
+            self.banks = torch.from_numpy(np.concatenate(parts)).to(self.device)
 
     def __len__(self):
         return len(self.paths) // self.batch_size                  # batches per epoch (drop_last=True)
 
     def draw(self, indices):
-        """Crop positions for the given items, in order (model/dataset.py:41,48): (step_begin [B], begin [B])."""
-        steps = np.array([int(self.random.randint(self.lengths[i] - self.sequence_length)) // HOP_LENGTH for i in indices],
-                         dtype=np.int64)
-        return steps, steps * HOP_LENGTH
+        """Crop positions and shifts for the given items, in order (model/dataset.py:41,48; augment.draw_items):
+        (step_begin [B], begin [B], shift [B]).  Without pitch_shift the crop stream is used exactly as before and shift is 0."""
+        steps, shifts = augment.draw_items(self.random, self.aug if self.pitch_shift else None, self.lengths, indices,
+                                           self.sequence_length, self.pitch_shift)
+        return steps, steps * HOP_LENGTH, shifts
 
-    def batch(self, indices):
-        """One decoded batch on the device for the given track indices (len == batch_size)."""
-        indices = [int(i) for i in indices]
-        b = len(indices)
-        steps, begins = self.draw(indices)
+    def _upload(self, fill):
+        """The next pinned staging buffer, filled by `fill(staging)`, on its way to the device."""
         slot = self._ring_pos
         self._ring_pos = (slot + 1) % len(self._ring)
         if self._ring_events[slot] is not None:
             self._ring_events[slot].synchronize()
         staging = self._ring[slot]
-        staging[0, :b] = torch.from_numpy(self.a_off[indices] + begins)
-        staging[1, :b] = torch.from_numpy(self.l_off[indices] + steps * self.n_keys)
-        dev_begins = staging[:, :b].to(self.device, non_blocking=True)
+        dev = fill(staging).to(self.device, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         self._ring_events[slot] = ev
+        return dev
+
+    def crop(self, indices, steps, shifts=None):
+        """The batch of the given items cropped at source rows `steps` (any row of the track) and transposed by `shifts` semitones
+        (None: no shift); what batch() calls with the drawn positions."""
+        indices = [int(i) for i in indices]
+        b = len(indices)
+        if b < 1 or b > self.batch_size:
+            raise ValueError(f'crop: {b} items, expected 1..{self.batch_size}')
+        steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+        shifts = np.zeros(b, dtype=np.int64) if shifts is None else np.asarray(shifts, dtype=np.int64).reshape(-1)
+        if len(steps) != b or len(shifts) != b:
+            raise ValueError('crop: one step and one shift per item')
+        begins = steps * HOP_LENGTH
         n_steps = self.sequence_length // HOP_LENGTH
         out = {'audio': torch.empty((b, self.sequence_length), device=self.device, dtype=torch.float32)}
         for k in ('onset', 'offset', 'frame', 'velocity'):
             out[k] = torch.empty((b, n_steps, self.n_keys), device=self.device, dtype=torch.float32)
-        call('rv_crop_segments', ptr(self.audio), ptr(self.label), ptr(self.velocity), ptr(dev_begins[0]), ptr(dev_begins[1]),
-             b, self.sequence_length, n_steps, self.n_keys, ptr(out['audio']), ptr(out['onset']), ptr(out['offset']),
-             ptr(out['frame']), ptr(out['velocity']), stream())
+        if not self.pitch_shift:
+            if shifts.any():
+                raise ValueError('crop: shifts need DeviceCorpus(pitch_shift > 0)')
+            if (steps < 0).any() or (begins + self.sequence_length > self.lengths[indices]).any():
+                raise ValueError('crop: a crop does not lie inside its track')
+
+            def fill(staging):
+                staging[0, :b] = torch.from_numpy(self.a_off[indices] + begins)
+                staging[1, :b] = torch.from_numpy(self.l_off[indices] + steps * self.n_keys)
+                return staging[:, :b]
+            dev_begins = self._upload(fill)
+            call('rv_crop_segments', ptr(self.audio), ptr(self.label), ptr(self.velocity), ptr(dev_begins[0]), ptr(dev_begins[1]),
+                 b, self.sequence_length, n_steps, self.n_keys, ptr(out['audio']), ptr(out['onset']), ptr(out['offset']),
+                 ptr(out['frame']), ptr(out['velocity']), stream())
+        else:
+            if (np.abs(shifts) > augment.MAX_SHIFT).any():
+                raise ValueError(f'crop: shifts must lie in -{augment.MAX_SHIFT}..{augment.MAX_SHIFT}')
+            if (steps < 0).any() or (steps >= self.n_rows[indices]).any():
+                raise ValueError('crop: a crop does not start inside its track')
+            table = np.zeros((b, ITEM_FIELDS), dtype=np.int64)
+            table[:, 0] = self.a_off[indices] + begins
+            table[:, 1] = self.a_off[indices]
+            table[:, 2] = self.a_off[indices] + self.lengths[indices]
+            table[:, 3:8] = [self._banks[int(k)] for k in shifts]
+            table[:, 8] = self.l_off[indices] + steps * self.n_keys
+            table[:, 9] = self.n_rows[indices] - steps
+            table[:, 10] = shifts
+
+            def fill(staging):
+                staging[:b] = torch.from_numpy(table)
+                return staging[:b]
+            items = self._upload(fill)
+            call('rv_crop_segments_shift', ptr(self.audio), self.audio.numel(), ptr(self.label), ptr(self.velocity), self.label.numel(),
+                 ptr(self.banks), self.banks.numel(), ptr(items), b, self.sequence_length, n_steps, self.n_keys, ptr(out['audio']),
+                 ptr(out['onset']), ptr(out['offset']), ptr(out['frame']), ptr(out['velocity']), stream())
+        out['shift'] = torch.from_numpy(shifts.copy())
         out['path'] = [self.paths[i] for i in indices]
         out['start_idx'] = torch.from_numpy(begins)
         return out
+
+    def batch(self, indices):
+        """One decoded batch on the device for the given track indices (len == batch_size)."""
+        indices = [int(i) for i in indices]
+        steps, _, shifts = self.draw(indices)
+        return self.crop(indices, steps, shifts)
 
     def __iter__(self):
         """One epoch: a random permutation of the tracks in batches of batch_size, last partial batch dropped."""
@@ -113,8 +188,9 @@ class DeviceCorpus:
             yield self.batch(perm[i:i + self.batch_size])
 
 
-def device_loader(dataset, batch_size, device, rank=0, world=1, seed=42):
+def device_loader(dataset, batch_size, device, rank=0, world=1, seed=42, pitch_shift=0):
     """DeviceCorpus over the in-memory tracks of a PianoRollAudioDataset (``dataset.data``); with world > 1 every rank
-    keeps a disjoint shard (tracks rank, rank + world, ...) and its own item-order stream."""
+    keeps a disjoint shard (tracks rank, rank + world, ...) and its own item-order stream -- and, with ``pitch_shift``, its own
+    stream of shifts (seeded from the rank's crop seed)."""
     return DeviceCorpus(dataset.data, dataset.sequence_length, batch_size, device, seed=seed, rank=rank, world=world,
-                        sampler_seed=rank)
+                        sampler_seed=rank, pitch_shift=pitch_shift, aug_seed=1000003 + seed)
