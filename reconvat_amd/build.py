@@ -37,7 +37,7 @@ def _stale(target, deps):
 def _compile(src):
     obj = os.path.join(CSRC, os.path.splitext(src)[0] + '.o')
     path = os.path.join(CSRC, src)
-    deps = [path, os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'conv_shared.h')]
+    deps = [path] + [os.path.join(CSRC, n) for n in sorted(os.listdir(CSRC)) if n.endswith('.h')]
     extra, stale = [], _stale(obj, deps)
     if src == 'api.cpp':                       # carries the digest of ALL sources: rebuilt whenever any of them changed
         dig = source_digest()

@@ -23,7 +23,7 @@
 //
 // Weight gradients are pixel-reduction GEMMs (wgrad_mfma): per-wave partial sums are written to a
 // workspace and folded by a deterministic second pass (no atomics).
-#include "conv_shared.h"
+#include "conv_band.h"
 #include <mutex>
 
 // ------------------------------------------------------------------------------------------
@@ -693,8 +693,10 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_lds_k(ConvLdsArgs aa) {
 // pixels); lane (j, g) reads the 4x4 patch of tile j for channels 4g..4g+3 of the chunk straight from the staged band (16
 // ds_read_b128), transforms it in registers (32 adds per channel) and feeds V[xi] to the 16 x NT x 4 MFMAs of the chunk; the
 // transformed weights U[xi] = G g G^T come pre-packed (rv_pack_weights appends them behind the nine tap fragments).  The
-// accumulators hold M[xi] for xi = 0..15; the band epilogue applies A^T . A in registers and shares bias / statistics / fused
-// BatchNorm-backward / store logic with the direct form.  Unit staging (LDS-DMA, two buffers) is the direct kernel's, with the
+// accumulators hold M[xi] for xi = 0..15; the band epilogue applies A^T . A in registers and then REPEATS the bias / statistics / fused
+// BatchNorm-backward / store text of the direct form (a copy, and conv3x3_wino2_k holds a third: as shared functions the same text
+// changes the register allocation of most instances, profiles/band_epilogue_resources.txt; what the band kernels do share is the
+// host-side band plan, conv_band.h).  Unit staging (LDS-DMA, two buffers) is the direct kernel's, with the
 // band padded to an even width.
 // ------------------------------------------------------------------------------------------
 // HALF (families 0xANM: 8 waves, 0xCNM: 12 waves): the patch is read and transformed one HALF chunk (8 channels, two k-steps) at a time -- 32 instead of 64 patch
@@ -707,12 +709,11 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_lds_k(ConvLdsArgs aa) {
 // quad inside its piece is a permutation chosen for the READ side: lane (j, g) of the multiplying wave reads, for each of the 16 patch
 // elements, pixel X = 2 (tx_j + const) + const' -- neighbouring lanes are TWO pixels (128 bytes in a pixel-major image) apart, which
 // put the 16 lanes of a ds_read_b128 lane group on 4 of the 16 slots of a bank row (4-way conflict, 61 % of all LDS cycles in the
-// round-3 kernel).  Layout 1: slot = parity * 32 + (quad >> 1) * 16 + (pixel >> 1) * 2 + (quad & 1): the eight tiles x two quads
-// (g, g ^ 1) of a lane group land on sixteen different slots -- conflict-free.  Layout 0: even / odd pixel planes, pixel-major inside
-// a plane (slot = parity * 32 + (pixel >> 1) * 4 + quad): 2-way, every DMA lane quad still fetches 64 contiguous bytes.
+// round-3 kernel).  The layout (wino_slot, conv_shared.h): slot = parity * 32 + (quad >> 1) * 16 + (pixel >> 1) * 2 + (quad & 1): the eight
+// tiles x two quads (g, g ^ 1) of a lane group land on sixteen different slots -- conflict-free.
 // BNZ: the launch carries the fused BatchNorm-backward reduction (a.bn_z != NULL); its epilogue needs ~30 more registers, so the plain
 // launches get their own instance
-template <int NT, int MTW, int NW, bool HALF = false, int LAY = 1, bool BNZ = false>
+template <int NT, int MTW, int NW, bool HALF = false, bool BNZ = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv3x3_wino_k(ConvLdsArgs aa) {     // (four waves: the half-CU experiment family 0xE, two workgroups per CU -> <= 256 registers)
     constexpr int NTHR = NW * 64;
     constexpr int KC = 16;                       // channels per chunk
@@ -748,7 +749,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv3x3_wino_k(ConvL
     constexpr int TW = (NWF + NW - 1) / NW;
     const int nx = nrow * NP;
     int lp, lq;
-    wino_lane<LAY>(lane, lp, lq);
+    wino_lane(lane, lp, lq);
     // The input rows are fetched through a BUFFER RESOURCE over the input view: a lane whose byte offset lies outside it gets ZEROS
     // written to its LDS slot (measured: tools/probes/buffer_lds_oob.hip).  So "this lane is a halo column" and "this row is above /
     // below the image" are both just an offset bump of OOB = 0x40000000 (the view is < 0x3f000000 bytes: host check) -- no per-lane
@@ -868,8 +869,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv3x3_wino_k(ConvL
                 const unsigned tt = tv[m] ? (unsigned)t : 0u;
                 const int ty = (int)fastdiv(tt, a.fd_pw), tx = (int)tt - ty * WT;       // fd_pw divides by WT here
                 tyx[m] = (ty << 16) | tx;
-                lb0[m] = (2 * ty) * RP * 4 + wino_pair_off<LAY>(tx, g);
-                lb1[m] = (2 * ty) * RP * 4 + wino_pair_off<LAY>(tx + 1, g);
+                lb0[m] = (2 * ty) * RP * 4 + wino_pair_off(tx, g);
+                lb1[m] = (2 * ty) * RP * 4 + wino_pair_off(tx + 1, g);
 #pragma unroll
                 for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -2717,14 +2718,8 @@ static size_t conv3x3_lds_bytes(int R, int NT, int TH, int W, int nchunk, int nb
 template <int R, int NW, bool BF = false>
 static int launch_conv3x3_lds_r(const ConvArgs& a, int NT, int MTW, int TH, int wgs_per_cu, hipStream_t st) {
     ConvLdsArgs aa;
-    aa.c = a; aa.TH = TH; aa.nbands = cdiv(a.H, TH);
-    aa.total_bands = a.B * aa.nbands;
-    const int nsplit = a.ntile_n / NT;
-    int wgs = (256 * wgs_per_cu) / nsplit;
-    if (wgs < 1) wgs = 1;
-    if (wgs > aa.total_bands) wgs = aa.total_bands;
-    aa.bands_per_wg = cdiv(aa.total_bands, wgs);
-    wgs = cdiv(aa.total_bands, aa.bands_per_wg);
+    aa.c = a; aa.TH = TH;
+    dim3 grid(band_grid(aa, NT, 256 * wgs_per_cu)), blk(NW * 64);
     // RV_CONV_NBUF=3: a third unit buffer (prefetch distance 2) when it fits.  Measured neutral on MI355X (the
     // kernel is not DMA-latency bound), so two buffers -- less LDS -- stay the default.
     static const int nbuf_env = getenv("RV_CONV_NBUF") ? atoi(getenv("RV_CONV_NBUF")) : 0;
@@ -2734,9 +2729,6 @@ static int launch_conv3x3_lds_r(const ConvArgs& a, int NT, int MTW, int TH, int 
     static const int skew_env = getenv("RV_CONV_SKEW") ? atoi(getenv("RV_CONV_SKEW")) : 1;
     aa.skew = (aa.nbuf == 3 && NW >= 8) ? skew_env : 0;
     const size_t lds = conv3x3_lds_bytes(R, NT, TH, a.W, a.nchunk, aa.nbuf);
-    static const int xcd_env = getenv("RV_CONV_XCD") ? atoi(getenv("RV_CONV_XCD")) : 1;
-    aa.nsplit = nsplit; aa.xcd = xcd_env;
-    dim3 grid(wgs * nsplit), blk(NW * 64);
 #define RV_L3(nt, mt)                                                                              \
     if (NT == nt && MTW == mt) {                                                                  \
         auto kern = conv3x3_lds_k<R, nt, mt, NW, BF>;                                             \
@@ -2820,74 +2812,30 @@ static int launch_conv3x3_lds(const ConvArgs& a, int R, hipStream_t st, int forc
                   : launch_conv3x3_lds_r<2, 4>(a, best_nt, best_mt, best_th, best_wpc, st);
 }
 
-// Winograd launch (families 0x6NM: 8 waves, 0xANM / 0xCNM: 8 / 12 waves with the half-chunk patch): a band of TH (even) rows holds (TH/2) x ceil(W/2) tiles of 2x2 outputs,
-// NW x MTW groups of 16 tiles per unit.  force_th = 0: as many rows as the tile slots hold.
-static size_t conv3x3_wino_bytes(int NT, int TH, int W, int wbufs) {
-    const int NP = (2 * ((W + 1) / 2) + 2 + 15) / 16;            // 1 KiB pieces (16 pixels x 16 channels) per staged row
-    return (size_t)2 * (TH + 2) * NP * 1024 + (size_t)wbufs * 16 * NT * 1024;
-}
-
+// Winograd launch (families 0x6NM: 8 waves, 0xANM / 0xCNM: 8 / 12 waves with the half-chunk patch); the band plan is wino_band_plan (conv_band.h).
 // cap / wg_slots: LDS budget of a workgroup and workgroup slots on the chip -- 154 KiB and 256 (one workgroup per CU) for the shipped families;
 // 78 KiB and 512 for the half-CU experiment family 0xE (round 6: two four-wave workgroups per CU, possibly of two different kernels)
-template <int NW, bool HALF = false, int LAY = 1>
+template <int NW, bool HALF = false>
 static int launch_conv3x3_wino(const ConvArgs& a0, int NT, int MTW, int force_th, hipStream_t st, size_t cap = 154 * 1024, int wg_slots = 256) {
-    if (NT < 1 || a0.ntile_n % NT) return RV_EUNSUPPORTED;
-    if (NW == 12 && a0.bn_z) return RV_EUNSUPPORTED;      // the fused BatchNorm-backward epilogue does not fit three waves per SIMD without scratch
-    ConvLdsArgs aa;
-    aa.c = a0;
-    const long in_bytes = (((long)a0.B * a0.H * a0.W - 1) * a0.in_ld + a0.Cin) * 4;
-    if (in_bytes >= 0x3f000000L) return RV_EUNSUPPORTED;      // the staging loads address the input view with 30-bit offsets (see the kernel)
-    aa.in_bytes = (unsigned)in_bytes;
-    const int WT = (a0.W + 1) / 2;
-    aa.c.fd_pw = fastdiv_make((unsigned)WT);
-    int trows = (NW * MTW * 16) / WT;
-    if (trows < 1) return RV_EUNSUPPORTED;
-    int TH = 2 * trows;
-    if (TH > a0.H) TH = (a0.H + 1) & ~1;
-    if (force_th) {
-        if (force_th > TH || (force_th & 1)) return RV_EUNSUPPORTED;
-        TH = force_th;
-    }
-    // weights: resident for the whole kernel when all chunks fit next to the two band buffers (no weight DMA after unit 0, 16 NT KiB less
-    // L2 traffic per unit); else double-buffered per chunk like the band
+    // weights: resident for the whole kernel when all chunks fit next to the two band buffers, else double-buffered per chunk like the band
     static const int wres_env = getenv("RV_WINO_WRES") ? atoi(getenv("RV_WINO_WRES")) : 1;
-    aa.wres = 0;
-    size_t lds = conv3x3_wino_bytes(NT, TH, a0.W, a0.nchunk > 1 ? 2 : 1);
-    // "as many rows as the tile slots hold" (force_th == 0) also means: as many as the LDS holds (a staged row is a whole number of
-    // 1 KiB pieces, so e.g. a 114-pixel row takes 8 KiB)
-    while (!force_th && lds > cap && TH > 2) {
-        TH -= 2;
-        lds = conv3x3_wino_bytes(NT, TH, a0.W, a0.nchunk > 1 ? 2 : 1);
-    }
-    if (a0.nchunk > 1 && wres_env) {
-        const size_t lds_res = conv3x3_wino_bytes(NT, TH, a0.W, a0.nchunk);
-        if (lds_res <= cap) { aa.wres = 1; lds = lds_res; }
-    }
-    if (lds > cap) return RV_EUNSUPPORTED;
-    aa.TH = TH; aa.nbands = cdiv(a0.H, TH);
-    aa.total_bands = a0.B * aa.nbands;
-    const int nsplit = a0.ntile_n / NT;
-    int wgs = wg_slots / nsplit;
-    if (wgs < 1) wgs = 1;
-    if (wgs > aa.total_bands) wgs = aa.total_bands;
-    aa.bands_per_wg = cdiv(aa.total_bands, wgs);
-    wgs = cdiv(aa.total_bands, aa.bands_per_wg);
-    aa.nbuf = 2; aa.skew = 0;
+    ConvLdsArgs aa;
+    dim3 grid, blk(NW * 64);
+    size_t lds;
+    const int rc = wino_band_plan(aa, grid, lds, a0, NT, MTW, NW, force_th, cap, wg_slots, WinoWeightPolicy{2, false, wres_env != 0});
+    if (rc != RV_OK) return rc;
     aa.ablate = getenv("RV_ABLATE") ? atoi(getenv("RV_ABLATE")) : 0;
-    static const int xcd_env = getenv("RV_CONV_XCD") ? atoi(getenv("RV_CONV_XCD")) : 1;
-    aa.nsplit = nsplit; aa.xcd = xcd_env;
-    dim3 grid(wgs * nsplit), blk(NW * 64);
 #define RV_WN(nt, mt)                                                                              \
     if (NT == nt && MTW == mt) {                                                                  \
         static std::once_flag attr_once;                                                          \
         std::call_once(attr_once, [] {                                                            \
-            if (hipFuncSetAttribute((const void*)conv3x3_wino_k<nt, mt, NW, HALF, LAY, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) \
+            if (hipFuncSetAttribute((const void*)conv3x3_wino_k<nt, mt, NW, HALF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) \
                 (void)hipGetLastError();                                                          \
-            if (hipFuncSetAttribute((const void*)conv3x3_wino_k<nt, mt, NW, HALF, LAY, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) \
+            if (hipFuncSetAttribute((const void*)conv3x3_wino_k<nt, mt, NW, HALF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) \
                 (void)hipGetLastError();                                                          \
         });                                                                                       \
-        if (a0.bn_z) hipLaunchKernelGGL((conv3x3_wino_k<nt, mt, NW, HALF, LAY, true>), grid, blk, lds, st, aa);  \
-        else hipLaunchKernelGGL((conv3x3_wino_k<nt, mt, NW, HALF, LAY, false>), grid, blk, lds, st, aa);         \
+        if (a0.bn_z) hipLaunchKernelGGL((conv3x3_wino_k<nt, mt, NW, HALF, true>), grid, blk, lds, st, aa);  \
+        else hipLaunchKernelGGL((conv3x3_wino_k<nt, mt, NW, HALF, false>), grid, blk, lds, st, aa);         \
         return RV_OK;                                                                             \
     }
     // (instantiated: the tiles that fit the register file without scratch -- 64 accumulator registers per (tile group, n-tile) pair)

@@ -109,27 +109,31 @@ template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N > 15 ? 15 : N) : "memory");
 }
 
-template <int LAY> __device__ __forceinline__ int wino_slot(int p, int q) {
-    return LAY == 1 ? (p & 1) * 32 + (q >> 1) * 16 + (p >> 1) * 2 + (q & 1) : (p & 1) * 32 + (p >> 1) * 4 + q;
+// Winograd LDS image: 16-byte slot, inside its 1 KiB piece, of channel quad q of pixel p (see conv3x3_wino_k).  No caller: it documents
+// the image that wino_lane (DMA side) and wino_pair_off (read side) implement.
+__device__ __forceinline__ int wino_slot(int p, int q) {
+    return (p & 1) * 32 + (q >> 1) * 16 + (p >> 1) * 2 + (q & 1);
 }
 // ... and its inverse for the DMA side: (pixel of the piece, quad) that lane i fetches
-template <int LAY> __device__ __forceinline__ void wino_lane(int i, int& p, int& q) {
-    if (LAY == 1) { p = ((i >> 1) & 7) * 2 + (i >> 5); q = ((i >> 4) & 1) * 2 + (i & 1); }
-    else { p = ((i >> 2) & 7) * 2 + (i >> 5); q = i & 3; }
+__device__ __forceinline__ void wino_lane(int i, int& p, int& q) {
+    p = ((i >> 1) & 7) * 2 + (i >> 5); q = ((i >> 4) & 1) * 2 + (i & 1);
 }
 // byte offset, inside a row, of quad g of the pixel pair index u = X >> 1 (even pixel; the odd one is 512 bytes further)
-template <int LAY> __device__ __forceinline__ int wino_pair_off(int u, int g) {
-    return (u >> 3) * 1024 + (LAY == 1 ? (g >> 1) * 256 + (u & 7) * 32 + (g & 1) * 16 : (u & 7) * 64 + g * 16);
+__device__ __forceinline__ int wino_pair_off(int u, int g) {
+    return (u >> 3) * 1024 + ((g >> 1) * 256 + (u & 7) * 32 + (g & 1) * 16);     // (grouping: piece + lane term, the adds behind lb0 / lb1 follow it)
 }
 
 // packed f32 add / subtract on channel pairs (v_pk_add_f32, the subtraction as a neg modifier)
 __device__ __forceinline__ f32x2 pk_add(const f32x2 a, const f32x2 b) { return a + b; }
 __device__ __forceinline__ f32x2 pk_sub(const f32x2 a, const f32x2 b) { return a - b; }
+// (f32x4: two v_pk_add_f32 by hand -- left to the compiler, a <4 x float> add or subtraction is scalarised or scheduled differently)
 __device__ __forceinline__ f32x4 pk_add(const f32x4 a, const f32x4 b) {
-    const f32x2 lo = (f32x2){a[0], a[1]} + (f32x2){b[0], b[1]}, hi = (f32x2){a[2], a[3]} + (f32x2){b[2], b[3]};
+    f32x2 lo, hi;
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"((f32x2){a[0], a[1]}), "v"((f32x2){b[0], b[1]}));
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"((f32x2){a[2], a[3]}), "v"((f32x2){b[2], b[3]}));
     return (f32x4){lo[0], lo[1], hi[0], hi[1]};
 }
-__device__ __forceinline__ f32x4 pk_sub(const f32x4 a, const f32x4 b) {      // (left to the compiler, a <4 x float> fsub is scalarised)
+__device__ __forceinline__ f32x4 pk_sub(const f32x4 a, const f32x4 b) {
     f32x2 lo, hi;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(lo) : "v"((f32x2){a[0], a[1]}), "v"((f32x2){b[0], b[1]}));
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(hi) : "v"((f32x2){a[2], a[3]}), "v"((f32x2){b[2], b[3]}));

@@ -1,7 +1,7 @@
 // Winograd F(2x2, 3x3) convolution, software-pipelined (round 5): algo families 0x8NM / 0x9NM (8 waves, full / half-chunk patch) and
 // 0xBNM / 0xDNM (4 waves = one per SIMD, 512 registers) of rv_conv_fwd.  Replaces every 3x3 Conv2d / ConvTranspose2d forward and
 // input gradient of the U-Nets (reference model/UNet_onset.py:186-224) that conv3x3_wino_k (conv.hip) serves; same math, same LDS image,
-// same staging, same epilogue -- a different SCHEDULE.
+// same staging, the same host-side band plan (wino_band_plan, conv_band.h), a copy of its band epilogue -- a different SCHEDULE.
 //
 // What round 4's kernel left on the table (profiles/r04_pmc_winograd.txt: matrix pipe busy 0.365 / 0.419): inside a unit every wave ran
 // [patch ds_reads -> wait -> 64 packed transform adds -> 64 MFMAs] strictly in that order, and since the unit barrier lines all waves of a
@@ -16,21 +16,12 @@
 // registers) and buffer u%2 can be refilled for unit u+2 right behind it.  The weights of unit u are still being read during that
 // stage, so they never share the band's double buffer: either all chunks are resident, or they travel through a ring of three.
 // Tile geometry is per kernel, not per band (the tile -> LDS offsets do not depend on the band; only the validity of a row pair does).
-#include "conv_shared.h"
+#include "conv_band.h"
 #include <mutex>
 
 #ifndef RV_W2_SIDE
 #define RV_W2_SIDE 2
 #endif
-
-// (the compiler scalarises a <4 x float> add just like the subtraction: two v_pk_add_f32 by hand)
-__device__ __forceinline__ f32x2 pk2_add(const f32x2 a, const f32x2 b) { return a + b; }
-__device__ __forceinline__ f32x4 pk2_add(const f32x4 a, const f32x4 b) {
-    f32x2 lo, hi;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"((f32x2){a[0], a[1]}), "v"((f32x2){b[0], b[1]}));
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"((f32x2){a[2], a[3]}), "v"((f32x2){b[2], b[3]}));
-    return (f32x4){lo[0], lo[1], hi[0], hi[1]};
-}
 
 // AB: timing ablations (wrong results by design; instantiated only in -DRV_W2_DEV builds, selected with RV_W2_ABL=mask):
 //   1 no MFMAs | 2 no patch reads / transforms | 4 no weight-fragment reads | 8 no unit barrier | 16 no staging after the prologue |
@@ -40,7 +31,6 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino2_k(ConvLdsArgs aa) {
     constexpr int NTHR = NW * 64;
     constexpr int KC = 16;                       // channels per chunk
     constexpr int WFLOATS = 16 * NT * 256;       // 16 xi x NT fragments x 64 lanes x 4 floats
-    constexpr int LAY = 1;
     const ConvArgs& a = aa.c;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino2_k(ConvLdsArgs aa) {
     constexpr int TW = (NWF + NW - 1) / NW;
     const int nx = nrow * NP;
     int lp, lq;
-    wino_lane<LAY>(lane, lp, lq);
+    wino_lane(lane, lp, lq);
     constexpr unsigned OOB = 0x40000000u;
     const unsigned img_bytes = (unsigned)(((H * W - 1) * a.in_ld + KC) * 4);
     const long img_stride = (long)H * W * a.in_ld * 4;
@@ -161,8 +151,8 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino2_k(ConvLdsArgs aa) {
         const unsigned tt = tin[m] ? (unsigned)t : 0u;
         const int ty = (int)fastdiv(tt, a.fd_pw), tx = (int)tt - ty * WT;       // fd_pw divides by WT here
         tyx[m] = (ty << 16) | tx;
-        lb0[m] = (2 * ty) * RP * 4 + wino_pair_off<LAY>(tx, g);
-        lb1[m] = (2 * ty) * RP * 4 + wino_pair_off<LAY>(tx + 1, g);
+        lb0[m] = (2 * ty) * RP * 4 + wino_pair_off(tx, g);
+        lb1[m] = (2 * ty) * RP * 4 + wino_pair_off(tx + 1, g);
     }
     __shared__ __attribute__((aligned(16))) float cf[4 * 64];
     if (BNZ) {
@@ -201,12 +191,12 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino2_k(ConvLdsArgs aa) {
         constexpr int cc = decltype(ccc)::value, q = decltype(qc)::value;
         if constexpr (q == 0) T[cc] = pk_sub(T[cc], T[8 + cc]);
         if constexpr (q == 1) T[12 + cc] = pk_sub(T[4 + cc], T[12 + cc]);
-        if constexpr (q == 2) { const pvec s = pk2_add(T[4 + cc], T[8 + cc]); T[8 + cc] = pk_sub(T[8 + cc], T[4 + cc]); T[4 + cc] = s; }
+        if constexpr (q == 2) { const pvec s = pk_add(T[4 + cc], T[8 + cc]); T[8 + cc] = pk_sub(T[8 + cc], T[4 + cc]); T[4 + cc] = s; }
     };
     auto pass2 = [&](auto rrc, auto qc) {                // along patch row rr, into the operand registers
         constexpr int rr = decltype(rrc)::value, q = decltype(qc)::value;
         if constexpr (q == 0) d[4 * rr] = pk_sub(T[4 * rr], T[4 * rr + 2]);
-        if constexpr (q == 1) d[4 * rr + 1] = pk2_add(T[4 * rr + 1], T[4 * rr + 2]);
+        if constexpr (q == 1) d[4 * rr + 1] = pk_add(T[4 * rr + 1], T[4 * rr + 2]);
         if constexpr (q == 2) d[4 * rr + 2] = pk_sub(T[4 * rr + 2], T[4 * rr + 1]);
         if constexpr (q == 3) d[4 * rr + 3] = pk_sub(T[4 * rr + 1], T[4 * rr + 3]);
     };
@@ -451,11 +441,6 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_wino2_k(ConvLdsArgs aa) {
     }
 }
 
-static size_t wino2_bytes(int NT, int TH, int W, int wslots) {
-    const int NP = (2 * ((W + 1) / 2) + 2 + 15) / 16;
-    return (size_t)2 * (TH + 2) * NP * 1024 + (size_t)wslots * 16 * NT * 1024;
-}
-
 template <int NT, int MTW, int NW, bool HALF>
 static int launch_wino2(const ConvLdsArgs& aa, dim3 grid, size_t lds, hipStream_t st) {
     // (launches come from the autograd thread as well as from the main thread: once_flag, not a plain static bool)
@@ -474,49 +459,12 @@ static int launch_wino2(const ConvLdsArgs& aa, dim3 grid, size_t lds, hipStream_
 // A band of TH (even) rows holds (TH/2) x ceil(W/2) tiles of 2x2 outputs, NW x MTW groups of 16 tiles per unit.  force_th = 0: as many
 // rows as the tile slots (and the LDS) hold.
 int rv_launch_conv3x3_wino2(const ConvArgs& a0, int NT, int MTW, int nw, int half, int force_th, hipStream_t st) {
-    if (NT < 1 || a0.ntile_n % NT) return RV_EUNSUPPORTED;
     ConvLdsArgs aa;
-    aa.c = a0;
-    const long in_bytes = (((long)a0.B * a0.H * a0.W - 1) * a0.in_ld + a0.Cin) * 4;
-    if (in_bytes >= 0x3f000000L) return RV_EUNSUPPORTED;      // the staging loads address the input view with 30-bit offsets
-    aa.in_bytes = (unsigned)in_bytes;
-    const int WT = (a0.W + 1) / 2;
-    aa.c.fd_pw = fastdiv_make((unsigned)WT);
-    const int trows = (nw * MTW * 16) / WT;
-    if (trows < 1) return RV_EUNSUPPORTED;
-    int TH = 2 * trows;
-    if (TH > a0.H) TH = (a0.H + 1) & ~1;
-    if (force_th) {
-        if (force_th > TH || (force_th & 1)) return RV_EUNSUPPORTED;
-        TH = force_th;
-    }
-    const size_t cap = 154 * 1024;
-    // weights: resident when all chunks fit next to the two band buffers, else a ring of three chunk slots (the chunk of unit u is still
-    // being read while unit u+2 is on its way)
-    const int ring = a0.nchunk < 3 ? a0.nchunk : 3;
-    size_t lds = wino2_bytes(NT, TH, a0.W, ring);
-    while (!force_th && lds > cap && TH > 2) {
-        TH -= 2;
-        lds = wino2_bytes(NT, TH, a0.W, ring);
-    }
-    aa.wres = a0.nchunk <= 3 ? 1 : 0;
-    if (!aa.wres) {
-        const size_t lds_res = wino2_bytes(NT, TH, a0.W, a0.nchunk);
-        if (lds_res <= cap) { aa.wres = 1; lds = lds_res; }
-    }
-    if (lds > cap) return RV_EUNSUPPORTED;
-    aa.TH = TH; aa.nbands = cdiv(a0.H, TH);
-    aa.total_bands = a0.B * aa.nbands;
-    const int nsplit = a0.ntile_n / NT;
-    int wgs = 256 / nsplit;
-    if (wgs < 1) wgs = 1;
-    if (wgs > aa.total_bands) wgs = aa.total_bands;
-    aa.bands_per_wg = cdiv(aa.total_bands, wgs);
-    wgs = cdiv(aa.total_bands, aa.bands_per_wg);
-    aa.nbuf = 2; aa.skew = 0; aa.ablate = 0;
-    static const int xcd_env = getenv("RV_CONV_XCD") ? atoi(getenv("RV_CONV_XCD")) : 1;
-    aa.nsplit = nsplit; aa.xcd = xcd_env;
-    const dim3 grid(wgs * nsplit);
+    dim3 grid;
+    size_t lds;
+    // weights: resident when all chunks fit next to the two band buffers, else a ring of three chunk slots
+    const int rc = wino_band_plan(aa, grid, lds, a0, NT, MTW, nw, force_th, 154 * 1024, 256, WinoWeightPolicy{3, true, true});
+    if (rc != RV_OK) return rc;
 #define RV_W2(nt, mt, nwv, hf) \
     if (NT == nt && MTW == mt && nw == nwv && (half != 0) == hf) return launch_wino2<nt, mt, nwv, hf>(aa, grid, lds, st);
     // (instantiated: the tiles that fit the register file without scratch; the 8-wave NT = 2 tile does not carry the fused
@@ -535,7 +483,7 @@ int rv_launch_conv3x3_wino2(const ConvArgs& a0, int NT, int MTW, int nw, int hal
 #endif
     RV_W2(1, 1, 8, false) RV_W2(1, 1, 8, true) RV_W2(2, 1, 8, true) RV_W2(1, 2, 8, true)
     RV_W2(1, 2, 4, false) RV_W2(2, 1, 4, false)
-    if (nw == 12 && a0.bn_z) return RV_EUNSUPPORTED;       // (three waves per SIMD: no room for the fused BatchNorm-backward epilogue)
+    // (12 waves with the fused BatchNorm-backward epilogue: refused by wino_band_plan)
     if (NT == 1 && MTW == 1 && nw == 12 && half) {
         static std::once_flag attr12;
         std::call_once(attr12, [] { (void)hipFuncSetAttribute((const void*)conv3x3_wino2_k<1, 1, 12, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); });

@@ -352,11 +352,13 @@ def test_conv3x3_winograd_accumulate_and_colsum(dev, cin, cout, H, W, algo, monk
     assert rel_err(outs[0][2], outs[1][2]) < 1e-5
 
 
-def test_winograd_12_wave_tile_refuses_the_fused_bn_backward(dev, monkeypatch):
-    """Three waves per SIMD leave 168 registers: the fused BatchNorm-backward epilogue of the Winograd kernel does not fit them without
-    scratch, so that combination is refused (the tuner never offers it) instead of silently spilling."""
+@pytest.mark.parametrize('algo', ['0xc11', '0xd11', '0x921'])
+def test_winograd_12_wave_tile_refuses_the_fused_bn_backward(dev, monkeypatch, algo):
+    """Three waves per SIMD leave 168 registers: the fused BatchNorm-backward epilogue of the Winograd kernels (0xc11, and the pipelined
+    kernel's 0xd11) does not fit them without scratch, and neither does it fit the pipelined kernel's 8-wave NT = 2 half-chunk tile
+    (0x921), so those combinations are refused (the tuner never offers them) instead of silently spilling."""
     from reconvat_amd import ops, _lib
-    monkeypatch.setenv('RV_FORCE_ALGO', '0xc11')
+    monkeypatch.setenv('RV_FORCE_ALGO', algo)
     x = torch.rand(2, 10, 57, 32, device=dev)
     w = torch.rand(32, 32, 3, 3, device=dev)
     link = ops.BnLink()
