@@ -279,10 +279,19 @@ int rv_resample(const void* x, int in_dtype, long T_in, int C, long in_offset, c
  * rv_eval_frame_counts: ref / est uint8 rolls (8-byte aligned, non-zero = on) -> out[14] int64 (device): for the plain set and then
  *   for the chroma set the sums over frames of c, n_ref, n_est, min(n_ref, n_est) - c, max(0, n_ref - n_est), max(0, n_est - n_ref),
  *   max(n_ref, n_est) - c; plain c = |ref & est|, chroma c = sum over the 12 pitch classes (21 + key) % 12 of min(ref_k, est_k).
- *   Integer arithmetic only, partial sums added in a fixed order. */
+ *   Integer arithmetic only, partial sums added in a fixed order.
+ * rv_eval_decode_clean: rv_eval_decode with note clean-up.  bridge_gap = g, 0..31: per pitch, a maximal run of
+ *   inactive frames (neither roll on) of at most g frames that has an active frame directly before and directly after it counts as
+ *   active -- the starts, and rule1's look at the frame roll, stay those of the unbridged rolls, and a run that touches frame 0 or
+ *   frame T - 1 is never bridged.  min_frames = m, 1..32: a note runs from its start to the first inactive frame of the bridged
+ *   activity (T if none) and is written and painted only if end - start >= m; *count counts the written notes.  Same workspace,
+ *   same three launches, same order of the rows; rv_eval_decode is its (1, 0) case. */
 long rv_eval_workspace_bytes(long T);
 int rv_eval_decode(const float* onsets, const float* frames, long T, float onset_threshold, float frame_threshold, int rule, int* notes,
                    long max_notes, int* count, unsigned char* painted, void* workspace, long workspace_bytes, void* stream);
+int rv_eval_decode_clean(const float* onsets, const float* frames, long T, float onset_threshold, float frame_threshold, int rule,
+                         int min_frames, int bridge_gap, int* notes, long max_notes, int* count, unsigned char* painted, void* workspace,
+                         long workspace_bytes, void* stream);
 int rv_eval_frame_counts(const unsigned char* ref, const unsigned char* est, long T, long* out, void* workspace, long workspace_bytes,
                          void* stream);
 
@@ -296,8 +305,16 @@ int rv_eval_frame_counts(const unsigned char* ref, const unsigned char* est, lon
  * counts [n_on][n_fr][5] int64 (device): estimated notes; reference notes matched one-to-one to an estimate of the same pitch that
  *   starts within one frame (a maximum matching); the same with the offset test; frames painted by both; frames painted by the
  *   estimate -- each what rv_eval_decode + the host matcher + rv_eval_frame_counts give at that pair.  ref_totals [2] int64: n_ref,
- *   frames painted by the reference.  Two launches on `stream`, no host synchronisation, no atomics, deterministic. */
+ *   frames painted by the reference.  Two launches on `stream`, no host synchronisation, no atomics, deterministic.
+ * rv_eval_sweep_clean: rv_eval_sweep with the note clean-up of rv_eval_decode_clean applied to the ESTIMATE -- one (min_frames,
+ *   bridge_gap) per call, for the whole grid: the counters are those of the kept notes and their painted frames, and a candidate of the
+ *   matching is a kept note with its end in the bridged activity.  ref_notes / ref_roll are handed over decoded (by convention
+ *   without clean-up).  Same workspace, same two launches; rv_eval_sweep is its (1, 0) case. */
 long rv_eval_sweep_workspace_bytes(long T, int n_on, int n_fr);
+int rv_eval_sweep_clean(const float* onsets, const float* frames, long T, const float* onset_thresholds, int n_on,
+                        const float* frame_thresholds, int n_fr, int rule, int min_frames, int bridge_gap, const int* ref_notes, long n_ref,
+                        const unsigned char* ref_roll, long* counts, long* ref_totals, void* workspace, long workspace_bytes,
+                        void* stream);
 int rv_eval_sweep(const float* onsets, const float* frames, long T, const float* onset_thresholds, int n_on,
                   const float* frame_thresholds, int n_fr, int rule, const int* ref_notes, long n_ref, const unsigned char* ref_roll,
                   long* counts, long* ref_totals, void* workspace, long workspace_bytes, void* stream);

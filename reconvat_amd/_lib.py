@@ -77,9 +77,11 @@ SIGNATURES = {
     'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
     'rv_eval_workspace_bytes': (L, [L]),
     'rv_eval_decode': (I, [P, P, L, F, F, I, P, L, P, P, P, L, P]),
+    'rv_eval_decode_clean': (I, [P, P, L, F, F, I, I, I, P, L, P, P, P, L, P]),
     'rv_eval_frame_counts': (I, [P, P, L, P, P, L, P]),
     'rv_eval_sweep_workspace_bytes': (L, [L, I, I]),
     'rv_eval_sweep': (I, [P, P, L, P, I, P, I, I, P, L, P, P, P, P, L, P]),
+    'rv_eval_sweep_clean': (I, [P, P, L, P, I, P, I, I, I, I, P, L, P, P, P, P, L, P]),
     'rv_lstm_flag_bytes': (L, [I]),
     'rv_lstm_fwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'rv_lstm_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),

@@ -21,19 +21,49 @@ def _note_ends(active):
     return np.minimum.accumulate(idx[::-1], axis=0)[::-1]
 
 
-def extract_notes_wo_velocity(onsets, frames, onset_threshold=0.5, frame_threshold=0.5, rule='rule1'):
+MAX_MIN_FRAMES, MAX_BRIDGE_GAP = 32, 31         # the look-ahead / look-back of the device decoder stays inside one 64-frame tile
+
+
+def _cleanup_args(min_frames, bridge_gap):
+    """(min_frames, bridge_gap) as ints; ValueError unless they are integers in 1..32 and 0..31."""
+    for name, v, lo, hi in (('min_frames', min_frames, 1, MAX_MIN_FRAMES), ('bridge_gap', bridge_gap, 0, MAX_BRIDGE_GAP)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{name} must be an integer in {lo}..{hi}, got {v!r}')
+    return int(min_frames), int(bridge_gap)
+
+
+def _bridge_gaps(active, gap):
+    """``active`` [T, P] with every maximal inactive run of at most ``gap`` frames switched on, if it has an active frame directly
+    before it and directly after it (a run that touches frame 0 or frame T - 1 has not)."""
+    T = active.shape[0]
+    t = np.arange(T)[:, None]
+    before = np.maximum.accumulate(np.where(active, t, -1), axis=0)                     # last active frame <= t (-1 if none)
+    after = np.minimum.accumulate(np.where(active, t, T)[::-1], axis=0)[::-1]           # first active frame >= t (T if none)
+    return active | ((before >= 0) & (after < T) & (after - before - 1 <= gap))
+
+
+def extract_notes_wo_velocity(onsets, frames, onset_threshold=0.5, frame_threshold=0.5, rule='rule1', min_frames=1, bridge_gap=0):
     """model/decoding.py:4-56.  A note starts where the thresholded onset roll rises (rule1: and the frame roll is on)
     and lasts while the onset OR the frame roll stays on.  Returns (pitches [N], intervals [N, 2]) in frame units,
-    ordered by (onset frame, pitch) like the reference."""
+    ordered by (onset frame, pitch) like the reference.
+
+    Note clean-up (``min_frames=1, bridge_gap=0`` is the reference's decoder): ``bridge_gap`` = g, 0..31, switches on,
+    per pitch, every inactive run of the onset-OR-frame activity that is at most g frames long and lies between two active frames
+    -- the starts (and rule1's test of the frame roll) are those of the unbridged rolls; ``min_frames`` = m, 1..32, drops the notes
+    that end less than m frames after their start in the bridged activity."""
     if rule not in ('rule1', 'rule2'):
         raise NameError('Please enter the correct rule name')
+    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
     on, fr = _binarise(onsets, frames, onset_threshold, frame_threshold)
     onset_diff = np.concatenate([on[:1], on[1:] & ~on[:-1]], axis=0)
     if rule == 'rule1':
         onset_diff = onset_diff & fr
     t, p = np.nonzero(onset_diff)
-    ends = _note_ends(on | fr)[t, p]
-    keep = ends > t
+    active = on | fr
+    if bridge_gap:
+        active = _bridge_gaps(active, bridge_gap)
+    ends = _note_ends(active)[t, p]
+    keep = ends - t >= min_frames
     pitches = p[keep]
     intervals = np.stack([t[keep], ends[keep]], axis=1) if keep.any() else np.array([])
     return (pitches if keep.any() else np.array([])), intervals
@@ -77,14 +107,15 @@ def _device_roll(x):
     return x.clone() if x.data_ptr() % 16 else x
 
 
-def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_threshold=0.5, rule='rule1'):
-    """``extract_notes_wo_velocity`` on the device (csrc/eval.hip): the rolls stay in HBM, three launches decode them,
-    and the only read-back is the note count followed by that many (t, pitch, end) rows.  Returns (pitches, intervals, painted):
+def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_threshold=0.5, rule='rule1', min_frames=1, bridge_gap=0):
+    """``extract_notes_wo_velocity`` on the device (csrc/eval.hip): the rolls stay in HBM, three launches decode
+    them, and the only read-back is the note count followed by that many (t, pitch, end) rows.  Returns (pitches, intervals, painted):
     pitches / intervals are NumPy arrays equal to the host function's; painted is the uint8 [T, 88] roll of the notes -- what
     ``notes_to_frames`` paints -- left on the device for ``evaluate.evaluate_frames_device``."""
     from . import _lib
     if rule not in _RULES:
         raise NameError('Please enter the correct rule name')
+    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
     _lib.need_gpu(onsets, frames)
     on, fr = _device_roll(onsets), _device_roll(frames)
     if on.dim() != 2 or on.shape[1] != 88 or on.shape != fr.shape or on.device != fr.device:
@@ -97,11 +128,12 @@ def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_
         notes = torch.empty((max(max_notes, 1), 3), dtype=torch.int32, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
         painted = torch.empty((T, 88), dtype=torch.uint8, device=dev)
-        _lib.call('rv_eval_decode', on.data_ptr(), fr.data_ptr(), T, float(onset_threshold), float(frame_threshold), _RULES[rule],
-                  notes.data_ptr(), max_notes, count.data_ptr(), painted.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
+        _lib.call('rv_eval_decode_clean', on.data_ptr(), fr.data_ptr(), T, float(onset_threshold), float(frame_threshold), _RULES[rule],
+                  min_frames, bridge_gap, notes.data_ptr(), max_notes, count.data_ptr(), painted.data_ptr(), ws.data_ptr(), ws_bytes,
+                  _lib.stream())
         n = int(count.item())
     if n > max_notes:
-        raise RuntimeError(f'rv_eval_decode reported {n} notes, more than the bound of {max_notes}')
+        raise RuntimeError(f'rv_eval_decode_clean reported {n} notes, more than the bound of {max_notes}')
     if n == 0:
         return np.array([]), np.array([]), painted
     rows = notes[:n].cpu().numpy().astype(np.int64)

@@ -262,7 +262,7 @@ def _frames_to_eval_units(t, freqs):
 
 
 def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, save_path=None, reconstruction=True,
-                         onset=True, pseudo_onset=False, rule='rule2', VAT=False, device_metrics=False):
+                         onset=True, pseudo_onset=False, rule='rule2', VAT=False, device_metrics=False, min_frames=1, bridge_gap=0):
     """model/evaluate_functions.py:20-127: whole-song evaluation; returns a dict of lists with the reference's keys
     (losses, metric/note/*, metric/note-with-offsets/*, metric/frame/*, metric/MusicNet/micro_avg_P, and the *_2
     variants of the reconstruction pass).  ``save_path``: per song `<basename>.pred.mid` (the transcription, reconvat_amd/midi.py)
@@ -270,7 +270,13 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
 
     ``device_metrics=True`` computes the same dictionary where the posteriorgrams are: notes and painted rolls by
     ``extract_notes_wo_velocity_device``, frame metrics by ``evaluate_frames_device``, note matching by ``match_notes_sparse``, AP by
-    ``average_precision_device``; the per-frame lists of ``notes_to_frames`` are never built.  The model must be on a HIP device."""
+    ``average_precision_device``; the per-frame lists of ``notes_to_frames`` are never built.  The model must be on a HIP device.
+
+    ``min_frames`` / ``bridge_gap``: the note clean-up of ``extract_notes_wo_velocity``, applied to the decodes of the
+    estimate -- the ``_2`` pass included -- on either path; the labels are decoded without it."""
+    from .decoding import _cleanup_args
+    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)      # a bad value raises before any song is touched
+    clean = dict(min_frames=min_frames, bridge_gap=bridge_gap)
     from sklearn.metrics import average_precision_score
     metrics = defaultdict(list)
     for label in data:
@@ -289,10 +295,10 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
         if onset:
             p_ref, i_ref, *roll_ref = decode(lab_on, lab_fr, rule=rule)
             p_est, i_est, *roll_est = decode(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
-                                             frame_threshold, rule=rule)
+                                             frame_threshold, rule=rule, **clean)
         else:
             p_ref, i_ref, *roll_ref = decode(lab_fr, lab_fr, rule=rule)
-            p_est, i_est, *roll_est = decode(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule)
+            p_est, i_est, *roll_est = decode(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule, **clean)
         if not device_metrics:
             t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
             t_est, f_est = _frames_to_eval_units(*notes_to_frames(p_est, i_est, pred['frame'].shape))
@@ -319,7 +325,7 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
         metrics['metric/frame/f1'].append(hmean([frame_metrics['Precision'] + eps, frame_metrics['Recall'] + eps]) - eps)
         metrics['metric/MusicNet/micro_avg_P'].append(average_precision(pred['frame']))
         if reconstruction and pred.get('frame2') is not None:
-            p2, i2, *roll2 = decode(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold)
+            p2, i2, *roll2 = decode(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold, **clean)
             if not device_metrics:
                 t2, f2 = _frames_to_eval_units(*notes_to_frames(p2, i2, pred['frame2'].shape))
             p2, i2 = _to_eval_units(p2, i2)
@@ -361,12 +367,14 @@ def _sweep_grid(onset_thresholds, frame_thresholds):
     return on, fr
 
 
-def sweep_counts_host(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2'):
+def sweep_counts_host(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2', min_frames=1,
+                      bridge_gap=0):
     """The integer counters behind the note and frame metrics of one song at every pair of a threshold grid, by a plain loop over the
     host functions: the labels are decoded once at 0.5 / 0.5, the posteriorgrams at every pair (``extract_notes_wo_velocity``,
     float32 ``x > threshold``); ``match_notes`` without and with the offset test gives the two match counts, ``notes_to_frames`` the
     painted frames.  Returns int64 [n_on, n_fr] arrays ``n_est``, ``matched``, ``matched_with_offsets``, ``frame_tp`` (frames painted by
-    reference and estimate), ``frame_est``, and the ints ``n_ref`` and ``frame_ref``.  The yardstick of ``sweep_counts_device``."""
+    reference and estimate), ``frame_est``, and the ints ``n_ref`` and ``frame_ref``.  ``min_frames`` / ``bridge_gap`` clean
+    up the notes of the estimate, never those of the labels.  The yardstick of ``sweep_counts_device``."""
     on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
     shape = tuple(frame_ref.shape)
     p_ref, i_ref = extract_notes_wo_velocity(onset_ref, frame_ref, rule=rule)
@@ -375,7 +383,8 @@ def sweep_counts_host(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresh
     out = {k: np.zeros((len(on_thr), len(fr_thr)), np.int64) for k in SWEEP_KEYS}
     for a, t_on in enumerate(on_thr):
         for b, t_fr in enumerate(fr_thr):
-            p_est, i_est = extract_notes_wo_velocity(onset_pred, frame_pred, float(t_on), float(t_fr), rule=rule)
+            p_est, i_est = extract_notes_wo_velocity(onset_pred, frame_pred, float(t_on), float(t_fr), rule=rule, min_frames=min_frames,
+                                                     bridge_gap=bridge_gap)
             _, f_est = notes_to_frames(p_est, i_est, shape)
             pe, ie = _to_eval_units(p_est, i_est)
             out['n_est'][a, b] = len(pe)
@@ -408,15 +417,18 @@ def _offset_slack(intervals):
     return np.stack(slack, axis=1)
 
 
-def sweep_counts_device(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2'):
-    """``sweep_counts_host`` where the posteriorgrams are (csrc/eval.hip): same arguments, same result, two launches
-    for the whole grid.  The labels are decoded once by ``rv_eval_decode``; their notes go back to the device sorted by pitch with
-    the offset tolerance of each as a number of frames (``_offset_slack``), and ``rv_eval_sweep`` thresholds the rolls into bit masks
-    once per threshold and counts notes, matches and painted frames per pair.  Raises on a CPU tensor: no fallback."""
+def sweep_counts_device(onset_ref, frame_ref, onset_pred, frame_pred, onset_thresholds, frame_thresholds, rule='rule2', min_frames=1,
+                        bridge_gap=0):
+    """``sweep_counts_host`` where the posteriorgrams are (csrc/eval.hip): same arguments, same result, two
+    launches for the whole grid and one (min_frames, bridge_gap).  The labels are decoded once by ``rv_eval_decode_clean`` at (1, 0);
+    their notes go back to the device sorted by pitch with the offset tolerance of each as a number of frames (``_offset_slack``), and
+    ``rv_eval_sweep_clean`` thresholds the rolls into bit masks once per threshold and counts kept notes, matches and painted frames
+    per pair.  Raises on a CPU tensor: no fallback."""
     from . import _lib
-    from .decoding import _RULES, _device_roll
+    from .decoding import _RULES, _cleanup_args, _device_roll
     if rule not in _RULES:
         raise NameError('Please enter the correct rule name')
+    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
     on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
     _lib.need_gpu(onset_ref, frame_ref, onset_pred, frame_pred)
     p_ref, i_ref, roll_ref = extract_notes_wo_velocity_device(onset_ref, frame_ref, rule=rule)
@@ -434,15 +446,15 @@ def sweep_counts_device(onset_ref, frame_ref, onset_pred, frame_pred, onset_thre
     with torch.cuda.device(dev):
         ws_bytes = _lib.load().rv_eval_sweep_workspace_bytes(T, n_on, n_fr)
         if ws_bytes <= 0:
-            raise ValueError(f'rv_eval_sweep: no workspace for T = {T} and a {n_on} x {n_fr} grid')
+            raise ValueError(f'rv_eval_sweep_clean: no workspace for T = {T} and a {n_on} x {n_fr} grid')
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         thr = torch.from_numpy(np.concatenate([on_thr, fr_thr])).to(dev)
         ref_notes = torch.from_numpy(rows).to(dev)
         counts = torch.empty((n_on, n_fr, len(SWEEP_KEYS)), dtype=torch.int64, device=dev)
         totals = torch.empty(2, dtype=torch.int64, device=dev)
-        _lib.call('rv_eval_sweep', on.data_ptr(), fr.data_ptr(), T, thr.data_ptr(), n_on, thr.data_ptr() + 4 * n_on, n_fr, _RULES[rule],
-                  ref_notes.data_ptr(), n_ref, roll_ref.data_ptr(), counts.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws_bytes,
-                  _lib.stream())
+        _lib.call('rv_eval_sweep_clean', on.data_ptr(), fr.data_ptr(), T, thr.data_ptr(), n_on, thr.data_ptr() + 4 * n_on, n_fr,
+                  _RULES[rule], min_frames, bridge_gap, ref_notes.data_ptr(), n_ref, roll_ref.data_ptr(), counts.data_ptr(),
+                  totals.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream())
         counts, totals = counts.cpu().numpy(), totals.tolist()
     out = {k: np.ascontiguousarray(counts[:, :, c]) for c, k in enumerate(SWEEP_KEYS)}
     out['n_ref'], out['frame_ref'] = int(totals[0]), int(totals[1])
@@ -484,8 +496,11 @@ def best_threshold_index(values, onset_thresholds, frame_thresholds):
     return best[2], best[3]
 
 
+MAX_CLEANUPS = 8
+
+
 def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='note_f1', onset=True, pseudo_onset=False, rule='rule2',
-                    device_metrics=True, VAT=False):
+                    device_metrics=True, VAT=False, cleanups=((1, 0),)):
     """Choose ``onset_threshold`` / ``frame_threshold`` on a validation set.  One eval-mode ``run_on_batch`` per song of ``data`` (as
     in ``evaluate_wo_velocity``; ``onset`` / ``pseudo_onset`` / ``rule`` / ``VAT`` mean what they mean there), then the sweep counters of
     the song over the whole grid -- ``sweep_counts_device`` (``device_metrics=True``, model on a HIP device) or ``sweep_counts_host``
@@ -493,15 +508,25 @@ def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='
     songs with ``np.mean`` like the lists of ``evaluate_wo_velocity``: every grid value equals the mean of the matching
     ``evaluate_wo_velocity`` list at that pair.
 
+    ``cleanups``: 1..8 ``(min_frames, bridge_gap)`` pairs to choose among as well -- still one forward per song, then
+    one sweep per pair.
+
     Returns ``{'onset_thresholds', 'frame_thresholds', 'grid': {metric: float64 [n_on, n_fr]}, 'criterion', 'best_index': (a, b),
-    'onset_threshold', 'frame_threshold', 'best_value', 'songs'}``.  The best pair maximises ``grid[criterion]`` (``note_f1``,
-    ``note_with_offsets_f1`` or ``frame_f1``).  Ties go to the pair nearest (0.5, 0.5) in max-norm (distances compared after rounding
-    to 1e-6, so that 0.3 and 0.7 are equally far), then to the lowest onset index, then to the lowest frame index."""
+    'onset_threshold', 'frame_threshold', 'best_value', 'songs', 'cleanups', 'grids', 'best_cleanup', 'min_frames', 'bridge_gap'}``.
+    ``grids`` holds one grid dictionary per entry of ``cleanups``, ``best_cleanup`` is the index of the chosen entry and ``grid`` its
+    grid.  The best triple maximises ``grids[c][criterion][a, b]`` (``note_f1``, ``note_with_offsets_f1`` or ``frame_f1``).  Ties go to
+    the earliest entry of ``cleanups``, then to the pair nearest (0.5, 0.5) in max-norm (distances compared after rounding to 1e-6,
+    so that 0.3 and 0.7 are equally far), then to the lowest onset index, then to the lowest frame index."""
+    from .decoding import _cleanup_args
     if criterion not in SWEEP_CRITERIA:
         raise ValueError(f'criterion must be one of {SWEEP_CRITERIA}, got {criterion!r}')
     on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
+    cleanups = [tuple(c) for c in cleanups]
+    if not 1 <= len(cleanups) <= MAX_CLEANUPS or any(len(c) != 2 for c in cleanups):
+        raise ValueError(f'cleanups must hold 1..{MAX_CLEANUPS} (min_frames, bridge_gap) pairs, got {cleanups}')
+    cleanups = [_cleanup_args(*c) for c in cleanups]
     sweep = sweep_counts_device if device_metrics else sweep_counts_host
-    per_song = defaultdict(list)
+    per_song = [defaultdict(list) for _ in cleanups]
     for label in data:
         pred, _, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
         frame = pred['frame'].detach().squeeze(0).relu()
@@ -509,26 +534,31 @@ def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='
         if device_metrics:
             lab_on, lab_fr = lab_on.to(frame.device), lab_fr.to(frame.device)
         if onset:
-            est_on = lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu()
-            counts = sweep(lab_on, lab_fr, est_on, frame, on_thr, fr_thr, rule=rule)
+            rolls = (lab_on, lab_fr, lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu(), frame)
         else:
-            counts = sweep(lab_fr, lab_fr, frame, frame, on_thr, fr_thr, rule=rule)
-        song = defaultdict(lambda: np.zeros((len(on_thr), len(fr_thr)), np.float64))
-        for a in range(len(on_thr)):
-            for b in range(len(fr_thr)):
-                for k, v in sweep_metrics(counts, a, b).items():
-                    song[k][a, b] = v
-        for k, v in song.items():
-            per_song[k].append(v)
-    if not per_song:
+            rolls = (lab_fr, lab_fr, frame, frame)
+        for (min_frames, bridge_gap), lists in zip(cleanups, per_song):
+            counts = sweep(*rolls, on_thr, fr_thr, rule=rule, min_frames=min_frames, bridge_gap=bridge_gap)
+            song = defaultdict(lambda: np.zeros((len(on_thr), len(fr_thr)), np.float64))
+            for a in range(len(on_thr)):
+                for b in range(len(fr_thr)):
+                    for k, v in sweep_metrics(counts, a, b).items():
+                        song[k][a, b] = v
+            for k, v in song.items():
+                lists[k].append(v)
+    if not per_song[0]:
         raise ValueError('tune_thresholds: no song in the validation set')
-    grid = {}
-    for k, v in per_song.items():                                       # np.mean of the per-song list, cell by cell: the scripts' average
-        grid[k] = np.array([[np.mean([song[a, b] for song in v]) for b in range(len(fr_thr))] for a in range(len(on_thr))])
-    a, b = best_threshold_index(grid[criterion], onset_thresholds, frame_thresholds)
-    return {'onset_thresholds': on_thr, 'frame_thresholds': fr_thr, 'grid': grid, 'criterion': criterion, 'best_index': (a, b),
-            'onset_threshold': float(on_thr[a]), 'frame_threshold': float(fr_thr[b]), 'best_value': float(grid[criterion][a, b]),
-            'songs': len(per_song[criterion])}
+    grids = []
+    for lists in per_song:                                              # np.mean of the per-song list, cell by cell: the scripts' average
+        grids.append({k: np.array([[np.mean([song[a, b] for song in v]) for b in range(len(fr_thr))] for a in range(len(on_thr))])
+                      for k, v in lists.items()})
+    best = [best_threshold_index(grid[criterion], onset_thresholds, frame_thresholds) for grid in grids]
+    c = int(np.argmax([grid[criterion][ab] for grid, ab in zip(grids, best)]))      # argmax: the earliest of equal values
+    a, b = best[c]
+    return {'onset_thresholds': on_thr, 'frame_thresholds': fr_thr, 'grid': grids[c], 'criterion': criterion, 'best_index': (a, b),
+            'onset_threshold': float(on_thr[a]), 'frame_threshold': float(fr_thr[b]), 'best_value': float(grids[c][criterion][a, b]),
+            'songs': len(per_song[0][criterion]), 'cleanups': cleanups, 'grids': grids, 'best_cleanup': c,
+            'min_frames': cleanups[c][0], 'bridge_gap': cleanups[c][1]}
 
 
 def save_pianoroll(path, onsets, frames, onset_threshold=0.5, frame_threshold=0.5, zoom=4):

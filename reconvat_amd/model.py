@@ -572,6 +572,14 @@ class UNet_Onset(_Base):
             losses['loss/train_r_norm_ul'] = r_norm_ul
         return predictions, losses, spec.squeeze(1)
 
+    def transcribe(self, batch):
+        """The onset and frame posteriorgrams of ``batch['audio']`` from one transcriber pass (what ``run_on_batch`` in eval mode
+        returns under the same keys); the reconstructor does not run."""
+        audio_label = batch['audio']
+        spec = self._front(audio_label, audio_label.shape[-1])
+        pianoroll, onset, _ = self.transcriber(spec)
+        return {'onset': onset, 'frame': pianoroll}
+
 
 class UNet(_Base):
     def __init__(self, ds_ksize, ds_stride, log=True, reconstruction=True, mode='imagewise', spec='CQT', device='cpu',

@@ -1,12 +1,13 @@
 """Whole-song evaluation after the model's forward: the host metric code against the device path, one synthetic song.
 
-    python tools/bench_eval.py [--frames 18750] [--host-repeats 3] [--device-repeats 10]
+    python tools/bench_eval.py [--frames 18750] [--host-repeats 3] [--device-repeats 10] [--min-frames 1] [--bridge-gap 0]
 
 The song: notes painted into label rolls (about one note per 3.2 frames, i.e. ~5 900 at the default ten minutes); the
 "posteriorgrams" are the labels shifted by one frame, scaled, plus noise.  Timed are steps 2 to 6 of evaluate_wo_velocity's loop
 (decoding, per-frame pitch lists, the two note matchings, frame metrics, AP) with the model excluded; every stage ends in a device
 synchronise, one warm-up run per path, then the median of the repeats.  Both paths run in this process on the same inputs and
-their results are compared before any time is printed."""
+their results are compared before any time is printed.  --min-frames / --bridge-gap: the note clean-up of the estimate's decode
+(DESIGN 3.13), on both paths."""
 import argparse
 import json
 import os
@@ -55,10 +56,13 @@ def note_metrics(ref, est, match):
             ev.evaluate_notes(i_ref, p_ref, i_est, p_est, match=match))
 
 
+CLEAN = dict(min_frames=1, bridge_gap=0)                               # set from the command line
+
+
 def host_path(s):
     c = Clock()
     ref, est = c.stage('decoding', lambda: (md.extract_notes_wo_velocity(s['onset'], s['frame'], rule='rule2'),
-                                            md.extract_notes_wo_velocity(s['pred_onset'], s['pred_frame'], rule='rule2')))
+                                            md.extract_notes_wo_velocity(s['pred_onset'], s['pred_frame'], rule='rule2', **CLEAN)))
     shape = s['frame'].shape
     lists = c.stage('per-frame pitch lists', lambda: (ev._frames_to_eval_units(*md.notes_to_frames(*ref, shape)),
                                                       ev._frames_to_eval_units(*md.notes_to_frames(*est, shape))))
@@ -71,7 +75,7 @@ def host_path(s):
 def device_path(s):
     c = Clock()
     ref, est = c.stage('decoding', lambda: (md.extract_notes_wo_velocity_device(s['onset'], s['frame'], rule='rule2'),
-                                            md.extract_notes_wo_velocity_device(s['pred_onset'], s['pred_frame'], rule='rule2')))
+                                            md.extract_notes_wo_velocity_device(s['pred_onset'], s['pred_frame'], rule='rule2', **CLEAN)))
     c.t['per-frame pitch lists'] = 0.0                                 # not built on this path
     notes = c.stage('note matching (two calls)', lambda: note_metrics(ref[:2], est[:2], ev.match_notes_sparse))
     frames = c.stage('frame metrics', lambda: ev.evaluate_frames_device(ref[2], est[2]))
@@ -92,7 +96,10 @@ def main():
     ap.add_argument('--frames', type=int, default=18750)
     ap.add_argument('--host-repeats', type=int, default=3)
     ap.add_argument('--device-repeats', type=int, default=10)
+    ap.add_argument('--min-frames', type=int, default=1)
+    ap.add_argument('--bridge-gap', type=int, default=0)
     a = ap.parse_args()
+    CLEAN.update(min_frames=a.min_frames, bridge_gap=a.bridge_gap)
     if not torch.cuda.is_available():
         raise SystemExit('bench_eval: needs a HIP device (the device path has no CPU fallback; a CPU timing says nothing about it)')
     dev = torch.device('cuda:0')
@@ -110,7 +117,7 @@ def main():
         print(f'{k:28s} {host_t[k]:10.4f} {dev_t[k]:10.4f} {ratio}')
     print(f'{"total":28s} {host_total:10.4f} {dev_total:10.4f} {host_total / dev_total:12.1f}')
     print(f'total, min..max over the runs: host {host_span[0]:.4f}..{host_span[1]:.4f}, device {dev_span[0]:.4f}..{dev_span[1]:.4f}')
-    print(json.dumps({'frames': a.frames, 'ref_notes': host_res[0], 'est_notes': host_res[1], 'identical': bool(same),
+    print(json.dumps({'frames': a.frames, 'min_frames': a.min_frames, 'bridge_gap': a.bridge_gap, 'ref_notes': host_res[0], 'est_notes': host_res[1], 'identical': bool(same),
                       'host_total_s': host_total, 'device_total_s': dev_total, 'host_stages_s': host_t, 'device_stages_s': dev_t}))
     if not same:
         raise SystemExit('bench_eval: the two paths disagree')

@@ -4,7 +4,10 @@
     python transcribe_files.py with device=cuda:0 weight=runs/.../model-final.pt input=Application/Input output=Application/Output
 
 ``onset_threshold=`` / ``frame_threshold=`` (default 0.5 each) set the decoding thresholds -- tune_thresholds.py chooses a pair on
-the validation split.
+the validation split.  ``min_frames=`` / ``bridge_gap=`` (default 1 / 0: off) clean the decoded notes up: gaps of at most
+``bridge_gap`` frames inside a note are bridged, notes shorter than ``min_frames`` frames are dropped.
+A checkpoint with an onset head (``transcriber.linear_onset.weight``) is loaded into ``UNet_Onset`` and decoded with its onset
+posteriorgram; any other checkpoint, and a run without ``weight=``, builds ``UNet``, whose frame roll serves as onset roll too.
 ``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
@@ -41,7 +44,8 @@ def load_audio(path, device='cpu'):
     return torch.from_numpy(read_audio_int16(path, device)).float().div(32768.0)
 
 
-def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT'):
+def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT', min_frames=1,
+                    bridge_gap=0):
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
         audio = load_audio(path, device).to(device)
@@ -49,9 +53,11 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
         if frame.is_cuda:                       # decode where the posteriorgrams are (csrc/eval.hip); same notes as the host decoder
-            p_est, i_est, _ = extract_notes_wo_velocity_device(onset, frame, onset_threshold, frame_threshold, rule=rule)
+            p_est, i_est, _ = extract_notes_wo_velocity_device(onset, frame, onset_threshold, frame_threshold, rule=rule,
+                                                               min_frames=min_frames, bridge_gap=bridge_gap)
         else:
-            p_est, i_est = extract_notes_wo_velocity(onset, frame, onset_threshold, frame_threshold, rule=rule)
+            p_est, i_est = extract_notes_wo_velocity(onset, frame, onset_threshold, frame_threshold, rule=rule, min_frames=min_frames,
+                                                     bridge_gap=bridge_gap)
         scaling = HOP_LENGTH / SAMPLE_RATE
         i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
         p_est = np.array([midi_to_hz(MIN_MIDI + m) for m in p_est])
@@ -60,20 +66,32 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
         print(f'midi_path = {midi_path}  ({len(p_est)} notes)')
 
 
+def load_model(weight, spec, device):
+    """The model of a checkpoint, in eval mode on `device`: ``UNet_Onset`` if the state dict has an onset head, else ``UNet`` -- and
+    ``UNet`` with fresh weights without a checkpoint.  The checkpoint's front-end buffers name its spectrogram."""
+    state = torch.load(weight, map_location='cpu') if weight else None
+    cls = ra.UNet
+    if state is not None:
+        spec = 'CQT' if 'spectrogram.cqt_kernels_real' in state else 'Mel'
+        if 'transcriber.linear_onset.weight' in state:
+            cls = ra.UNet_Onset
+    model = cls((2, 2), (2, 2), log=True, reconstruction=True, mode='imagewise', spec=spec, device=device)
+    if state is not None:
+        model.load_state_dict(state)
+    model.to(device).eval()
+    return model
+
+
 def main(argv):
     cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel', onset_threshold=0.5,
                frame_threshold=0.5)
-    cfg.update(parse_cli(argv))
-    state = torch.load(cfg['weight'], map_location='cpu') if cfg['weight'] else None
-    if state is not None:                       # the checkpoint's front-end buffers name its spectrogram
-        cfg['spec'] = 'CQT' if 'spectrogram.cqt_kernels_real' in state else 'Mel'
-    model = ra.UNet((2, 2), (2, 2), log=True, reconstruction=True, mode='imagewise', spec=cfg['spec'], device=cfg['device'])
-    if state is not None:
-        model.load_state_dict(state)
-    model.to(cfg['device']).eval()
+    given = parse_cli(argv)
+    cfg.update(given)
+    model = load_model(cfg['weight'], cfg['spec'], cfg['device'])
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
+    cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap') if k in given}        # handed on only when given
     transcribe2midi(files, model, cfg['device'], cfg['output'], onset_threshold=cfg['onset_threshold'],
-                    frame_threshold=cfg['frame_threshold'])
+                    frame_threshold=cfg['frame_threshold'], **cleanup)
 
 
 if __name__ == '__main__':
