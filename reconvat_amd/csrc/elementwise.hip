@@ -243,6 +243,7 @@ __global__ __launch_bounds__(256) void scale_by_clip_k(float* g, long n, const f
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) g[i] *= coef;
 }
 
+// (restated in tests/stream_cases.py: grid_for)
 static int grid_for(long n) { long b = (n + 255) / 256; return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096); }
 
 // ---------------------------------------------------------------------------------------------
@@ -380,6 +381,7 @@ int rv_vat_perturb_bwd(const float* g, const float* x, const float* d, long rows
     return RV_OK;
 }
 
+// one partial per 2 048 elements (restated in tests/stream_cases.py: reduce_parts)
 long rv_reduce_workspace_bytes(long n) { return ((n + 2047) / 2048) * 4; }
 
 // kind: 0 = BCE mean (p vs soft/hard target t), 1 = MSE mean, 2 = mean |p|, 3 = sqrt(sum p^2) (L2 norm)
@@ -428,6 +430,7 @@ __global__ void zero_floats_k(float* p, int n) {
 }
 
 // out[n] = sum_m x[m*ld + n]   (out is overwritten unless accumulate)
+// (rv_colsum below; its path choice and rows per thread are restated in tests/stream_cases.py: colsum_path)
 // out[i] (+)= sum over the RV_BN_NREP replicas of sums[rep][c0 + i], i < n, where `sums` is a BatchNorm statistics workspace of C channels
 // ([rep][2][C] fp64) that a conv's fused epilogue filled (rv_conv_fwd bn_sums): the per-channel sums of what the conv stored ARE the
 // column sums of its output -- the bias gradient of the layer that consumes that output as dY, without another pass over it.
@@ -490,6 +493,7 @@ __global__ __launch_bounds__(256) void colsum_fold_k(const float* ws, int nblk, 
     for (int b = 0; b < nblk; ++b) s += ws[(long)b * N + col];
     out[col] = accumulate ? out[col] + s : s;
 }
+// (restated in tests/stream_cases.py: colsum_ordered_blocks, colsum_ordered_launch)
 static long colsum_ordered_blocks(long M) {
     long nblk = (M + 255) / 256;
     return nblk > 1024 ? 1024 : (nblk < 1 ? 1 : nblk);
