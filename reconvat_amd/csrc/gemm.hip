@@ -130,8 +130,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[2]
                     if (nb + r >= a.N) continue;
                     float* cc = c + (long)r * a.scn;
                     if (atomic_k) { atomicAdd(cc, v[r]); continue; }
-                    *cc = a.accumulate ? *cc + v[r] : v[r];
-                    if (a.C2) a.C2[(long)m * a.sc2m + (long)(nb + r) * a.sc2n] = v[r];
+                    const float o = a.accumulate ? *cc + v[r] : v[r];
+                    *cc = o;
+                    if (a.C2) a.C2[(long)m * a.sc2m + (long)(nb + r) * a.sc2n] = o;      // the same values, also when accumulating
                 }
             }
         }
