@@ -3105,7 +3105,7 @@ static int conv_fwd_impl(int mode, const float* in, int in_ld, int B, int H, int
         *sums_done = true;
         return RV_OK;
     }
-    if (mode == 0 && algo != 1 && fam != 1) {
+    if (mode == 0 && algo != 1 && fam != 1 && fam != 5) {   // (0x5NM is refused below: it must not fall through to the default persistent kernel)
         const bool forced = (fam >= 2 && fam <= 4) || fam == 7;
         int rc3 = forced ? launch_conv3x3_lds(a, R, st, f_nt, f_mt, fam == 7 ? 12 : (fam == 4 ? 16 : (fam == 3 ? 8 : 4)), f_th, bf)
                          : launch_conv3x3_lds(a, R, st, 0, 0, 4, 0, bf);
