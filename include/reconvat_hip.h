@@ -257,6 +257,17 @@ int rv_crop_segments_shift(const short* audio, long n_audio, const unsigned char
                            const float* banks, long n_bank, const long* items, int B, long seq_len, int n_steps, int n_keys,
                            float* out_audio, float* onset, float* offset, float* frame, float* out_velocity, void* stream);
 
+/* Acoustic augmentation of the feed (reconvat_amd/acoustics.py has the definition): one FIR per item plus white noise,
+ *   y[b][m] = sum_{j < W} h[b][j] x[b][m + lead - j] + noise_b[m],  m < n,  x[b][.] read as zero outside [0, n) of its own row
+ * (by a select: whatever lies next to the row in memory never enters a sum).  x, y: B rows of n floats, row strides x_stride /
+ * y_stride >= n, not overlapping; h [B][W] float32, 16-byte aligned; W a multiple of 16 in [16, 8256], 0 <= lead < W,
+ * 1 <= n < 2^31, 1 <= B <= 65535.  seed, amp: DEVICE arrays [B], both null for no noise; else noise_b[m] = float32(t) * amp[b],
+ * t = (v & 0xFFFF) + (v >> 16) - 65535, v = lowbias32(seed[b] ^ lowbias32(m + 0x9E3779B9)), added with one float32 add.
+ * The sum runs on the f32 matrix pipe (Toeplitz x Hankel, nothing formed in memory) in an order fixed by W, lead and m: the bits
+ * of an output do not depend on B or on the item's place in the batch.  One launch, no atomics, allocation or synchronisation. */
+int rv_fir_items(const float* x, long x_stride, const float* h, int W, int lead, const unsigned* seed, const float* amp, int B, long n,
+                 float* y, long y_stride, void* stream);
+
 /* ---- audio ingest: rational-ratio polyphase FIR resampling with the channel downmix fused in.
  *   y[m] = sum_n x[n] h[m M - n L],  x[n] = mean over the C channels of input frame n (zero outside the signal), L/M = sr_out/sr_in
  * x: [T_in, C] interleaved frames, in_dtype 0 = int16 (scale 2^-15), 1 = int32 (2^-31), 2 = float32; it is the slice

@@ -73,6 +73,7 @@ SIGNATURES = {
     'rv_swap_floats': (I, [P, P, L, P]),
     'rv_crop_segments': (I, [P, P, P, P, P, I, L, I, I, P, P, P, P, P, P]),
     'rv_crop_segments_shift': (I, [P, L, P, P, L, P, L, P, I, L, I, I, P, P, P, P, P, P]),
+    'rv_fir_items': (I, [P, L, P, I, I, P, P, I, L, P, L, P]),
     'rv_resample_max_coeffs': (L, []),
     'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
     'rv_eval_workspace_bytes': (L, [L]),

@@ -33,7 +33,12 @@ saving_freq = 200
 OPTIM_OPTIONS = dict(weight_decay=0.0, ema_decay=0.0, clip_before_step=False)
 # augmentation of the device feed (device_feed=True only), off by default: every training item -- labelled and
 # unlabelled -- is transposed by a random whole number of semitones in [-pitch_shift, pitch_shift] (at most 6) while it is cropped
-FEED_OPTIONS = dict(pitch_shift=0)
+# -- and, with reverb_rt60 / eq_db / noise_db, recorded in a random room (RT60 up to reverb_rt60 seconds, an impulse
+# response of reverb_taps taps), through a random five-band equaliser of at most +-eq_db dB and over white noise between
+# noise_db - 20 and noise_db dBFS.  The labels are untouched.
+# reverb_taps: the largest of 1024 / 2048 / 4096 / 8192 whose two launches per step (labelled + unlabelled batch) measured under 5 % of
+# the training step (profiles/feed_acoustics.txt: 2 x 434 us of 19.75 ms = 4.4 % at 8192; 2.0 % at 4096)
+FEED_OPTIONS = dict(pitch_shift=0, reverb_rt60=0.0, eq_db=0.0, noise_db=None, reverb_taps=8192)
 
 
 def base_config(o, onset_script):
@@ -170,7 +175,7 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
                  clip_gradient_norm, validation_length, refresh, device, epoches, logdir, log, iteration, VAT_start, VAT,
                  XI, eps, reconstruction, graph, fused_optimizer, saving_freq, device_feed=True, model_complexity=48, model_name='onset_frame', VAT_mode='all',
                  logging_freq=logging_freq, dtype='fp32', device_metrics=True, tune_thresholds=False, weight_decay=0.0, ema_decay=0.0,
-                 clip_before_step=False, pitch_shift=0, **_unused):
+                 clip_before_step=False, pitch_shift=0, reverb_rt60=0.0, eq_db=0.0, noise_db=None, reverb_taps=FEED_OPTIONS['reverb_taps'], **_unused):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if not fused_optimizer and (weight_decay or ema_decay or clip_before_step):
@@ -185,6 +190,16 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         if not device_feed or not str(device).startswith('cuda'):
             raise SystemExit('pitch_shift is an option of the device feed (the batch is resampled while it is cropped in HBM): it needs '
                              'device_feed=True and device=cuda:N (the host DataLoader path stays the reference loop).')
+    acoustics = None
+    if reverb_rt60 or eq_db or noise_db is not None:
+        from .acoustics import Acoustics
+        try:
+            acoustics = Acoustics(rt60=reverb_rt60, eq_db=eq_db, noise_db=noise_db, taps=reverb_taps)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if not device_feed or not str(device).startswith('cuda'):
+            raise SystemExit('reverb_rt60, eq_db and noise_db are options of the device feed (the batch is filtered in HBM after it is '
+                             'cropped): they need device_feed=True and device=cuda:N (the host DataLoader path stays the reference loop).')
     if onset_script == 'thickstun':
         VAT = False                                        # train_baseline_Thickstun.py sets the VAT keys and never uses them
     if not str(device).startswith('cuda') or not torch.cuda.is_available():
@@ -208,11 +223,20 @@ def run_training(onset_script, spec, resume_iteration, train_on, batch_size, seq
         # corpus resident in HBM, batches cropped/decoded by rv_crop_segments (reconvat_amd/feed.py); the training loaders alone
         # are augmented: validation, test and threshold-tuning sets never are
         from .feed import device_loader
-        l_loader = device_loader(l_set, train_batch_size, device, rank=rank, world=world, seed=42 + rank, pitch_shift=pitch_shift)
-        ul_loader = device_loader(ul_set, batch_size, device, rank=rank, world=world, seed=43 + rank, pitch_shift=pitch_shift) if VAT else None
+        l_loader = device_loader(l_set, train_batch_size, device, rank=rank, world=world, seed=42 + rank, pitch_shift=pitch_shift,
+                                 acoustics=acoustics)
+        ul_loader = device_loader(ul_set, batch_size, device, rank=rank, world=world, seed=43 + rank, pitch_shift=pitch_shift,
+                                  acoustics=acoustics) if VAT else None
         if pitch_shift and rank == 0:
             print(f'Pitch-shift augmentation: every training item transposed by a random k in [-{pitch_shift}, {pitch_shift}] semitones')
+        if acoustics is not None and rank == 0:
+            print(f'Acoustic augmentation: every training item in a room of RT60 in [{0.25 * acoustics.rt60:g}, {acoustics.rt60:g}] s '
+                  f'({acoustics.taps} taps), equalised by up to +-{acoustics.eq_db:g} dB, noise floor '
+                  + ('off' if acoustics.noise_db is None else f'in [{acoustics.noise_db - 20:g}, {acoustics.noise_db:g}] dBFS'))
     else:
+        if acoustics is not None:
+            raise SystemExit(f'reverb_rt60, eq_db and noise_db need the device feed, and the {train_on} training set has no in-memory '
+                             'tracks to keep in HBM.')
         if pitch_shift:
             raise SystemExit(f'pitch_shift needs the device feed, and the {train_on} training set has no in-memory tracks to keep in HBM.')
         ul_loader = DataLoader(ul_set, batch_size, shuffle=True, drop_last=True) if VAT else None

@@ -13,10 +13,15 @@ There is no CPU fallback: the corpus tensors must live on a HIP device.
 
 ``pitch_shift=p`` (off by default; DESIGN 3.12, reconvat_amd/augment.py) makes every item a copy of its crop transposed by a random
 whole number of semitones in [-p, p]: ``rv_crop_segments_shift`` resamples the audio while it crops and moves the labels along.
+
+``acoustics=Acoustics(...)`` (off by default; DESIGN 3.14, reconvat_amd/acoustics.py) records every item in another room, through another
+microphone and over a noise floor: the crop, shifted or plain, goes to a scratch buffer and ``rv_fir_items`` filters it with the
+item's own FIR into the batch.  The labels, the crop stream and the pitch-shift stream are untouched.
 """
 import numpy as np
 import torch
 
+from . import acoustics as acu
 from . import augment
 from .constants import HOP_LENGTH
 from ._lib import call, ptr, stream, need_gpu
@@ -30,9 +35,12 @@ def _pad_to(n, m):
 
 class DeviceCorpus:
     def __init__(self, tracks, sequence_length, batch_size, device, seed=42, rank=0, world=1, sampler_seed=0, pitch_shift=0,
-                 aug_seed=0):
+                 aug_seed=0, acoustics=None, acoustics_seed=0):
         tracks = list(tracks)[rank::world]
         self.pitch_shift = augment.check_shift(pitch_shift)
+        if acoustics is not None and not isinstance(acoustics, acu.Acoustics):
+            raise ValueError(f'acoustics must be None or an Acoustics object (got {acoustics!r})')
+        self.acoustics = None if acoustics is None or acoustics.off else acoustics
         if not tracks:
             raise ValueError('DeviceCorpus: no tracks for this rank')
         self.sequence_length = int(sequence_length)
@@ -95,6 +103,14 @@ class DeviceCorpus:
                 parts.append(bank.reshape(-1))
                 at += bank.size                                    # Kp is a multiple of 4
             self.banks = torch.from_numpy(np.concatenate(parts)).to(self.device)
+        if self.acoustics is not None:
+            # a third stream for the acoustic parameters; the filters of a batch, then its noise seeds and amplitudes, travel through
+            # a pinned ring of their own: float32 [B W | B | B], the seeds as their bit patterns
+            self.acu = np.random.RandomState(acoustics_seed)
+            floats = self.batch_size * (self.acoustics.width + 2)
+            self._fir_ring = [torch.empty(floats, dtype=torch.float32).pin_memory() for _ in range(4)]
+            self._fir_events = [None] * len(self._fir_ring)
+            self._fir_pos = 0
 
     def __len__(self):
         return len(self.paths) // self.batch_size                  # batches per epoch (drop_last=True)
@@ -106,22 +122,40 @@ class DeviceCorpus:
                                            self.sequence_length, self.pitch_shift)
         return steps, steps * HOP_LENGTH, shifts
 
-    def _upload(self, fill):
-        """The next pinned staging buffer, filled by `fill(staging)`, on its way to the device."""
-        slot = self._ring_pos
-        self._ring_pos = (slot + 1) % len(self._ring)
-        if self._ring_events[slot] is not None:
-            self._ring_events[slot].synchronize()
-        staging = self._ring[slot]
+    def _upload(self, fill, fir=False):
+        """The next pinned staging buffer (of the filter ring with `fir`), filled by `fill(staging)`, on its way to the device."""
+        ring, events = (self._fir_ring, self._fir_events) if fir else (self._ring, self._ring_events)
+        slot = self._fir_pos if fir else self._ring_pos
+        if fir:
+            self._fir_pos = (slot + 1) % len(ring)
+        else:
+            self._ring_pos = (slot + 1) % len(ring)
+        if events[slot] is not None:
+            events[slot].synchronize()
+        staging = ring[slot]
         dev = fill(staging).to(self.device, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        self._ring_events[slot] = ev
+        events[slot] = ev
         return dev
 
-    def crop(self, indices, steps, shifts=None):
-        """The batch of the given items cropped at source rows `steps` (any row of the track) and transposed by `shifts` semitones
-        (None: no shift); what batch() calls with the drawn positions."""
+    def filters(self, params):
+        """float32 [b, W] filters, uint32 [b] noise seeds and float32 [b] noise amplitudes of the given parameter dicts."""
+        W = self.acoustics.width
+        h = np.zeros((len(params), W), dtype=np.float32)
+        for i, p in enumerate(params):
+            if int(p['taps']) != self.acoustics.taps:
+                raise ValueError(f"crop: acoustic parameters of {p['taps']} taps, the corpus was built for {self.acoustics.taps}")
+            h[i], lead = acu.item_filter(p)
+            assert lead == acu.LEAD
+        seeds = np.array([int(p['seed']) for p in params], dtype=np.uint32)
+        amps = np.array([p['amp'] for p in params], dtype=np.float32)
+        return h, seeds, amps
+
+    def crop(self, indices, steps, shifts=None, acoustics=None):
+        """The batch of the given items cropped at source rows `steps` (any row of the track), transposed by `shifts` semitones
+        (None: no shift) and recorded with the per-item parameter dicts `acoustics` (acoustics.draw; None: as cropped); what batch()
+        calls with what it drew."""
         indices = [int(i) for i in indices]
         b = len(indices)
         if b < 1 or b > self.batch_size:
@@ -132,7 +166,16 @@ class DeviceCorpus:
             raise ValueError('crop: one step and one shift per item')
         begins = steps * HOP_LENGTH
         n_steps = self.sequence_length // HOP_LENGTH
-        out = {'audio': torch.empty((b, self.sequence_length), device=self.device, dtype=torch.float32)}
+        if acoustics is not None:
+            if self.acoustics is None:
+                raise ValueError('crop: acoustic parameters need DeviceCorpus(acoustics=Acoustics(...)) with something switched on')
+            acoustics = list(acoustics)
+            if len(acoustics) != b:
+                raise ValueError('crop: one set of acoustic parameters per item')
+            fir_h, fir_seed, fir_amp = self.filters(acoustics)
+        audio = torch.empty((b, self.sequence_length), device=self.device, dtype=torch.float32)
+        # with acoustics the crop lands in `audio` as a scratch buffer and rv_fir_items writes the batch's audio from it
+        out = {'audio': audio}
         for k in ('onset', 'offset', 'frame', 'velocity'):
             out[k] = torch.empty((b, n_steps, self.n_keys), device=self.device, dtype=torch.float32)
         if not self.pitch_shift:
@@ -170,6 +213,19 @@ class DeviceCorpus:
             call('rv_crop_segments_shift', ptr(self.audio), self.audio.numel(), ptr(self.label), ptr(self.velocity), self.label.numel(),
                  ptr(self.banks), self.banks.numel(), ptr(items), b, self.sequence_length, n_steps, self.n_keys, ptr(out['audio']),
                  ptr(out['onset']), ptr(out['offset']), ptr(out['frame']), ptr(out['velocity']), stream())
+        if acoustics is not None:
+            W = self.acoustics.width
+
+            def fill_fir(staging):
+                staging[:b * W] = torch.from_numpy(fir_h.reshape(-1))
+                staging[b * W:b * W + b] = torch.from_numpy(fir_seed.view(np.float32))
+                staging[b * W + b:b * W + 2 * b] = torch.from_numpy(fir_amp)
+                return staging[:b * (W + 2)]
+            fir = self._upload(fill_fir, fir=True)
+            out['audio'] = torch.empty_like(audio)
+            call('rv_fir_items', ptr(audio), self.sequence_length, ptr(fir), W, acu.LEAD, ptr(fir) + 4 * b * W, ptr(fir) + 4 * (b * W + b),
+                 b, self.sequence_length, ptr(out['audio']), self.sequence_length, stream())
+            out['acoustics'] = acoustics
         out['shift'] = torch.from_numpy(shifts.copy())
         out['path'] = [self.paths[i] for i in indices]
         out['start_idx'] = torch.from_numpy(begins)
@@ -179,7 +235,8 @@ class DeviceCorpus:
         """One decoded batch on the device for the given track indices (len == batch_size)."""
         indices = [int(i) for i in indices]
         steps, _, shifts = self.draw(indices)
-        return self.crop(indices, steps, shifts)
+        drawn = [acu.draw(self.acu, self.acoustics) for _ in indices] if self.acoustics is not None else None
+        return self.crop(indices, steps, shifts, drawn)
 
     def __iter__(self):
         """One epoch: a random permutation of the tracks in batches of batch_size, last partial batch dropped."""
@@ -188,9 +245,10 @@ class DeviceCorpus:
             yield self.batch(perm[i:i + self.batch_size])
 
 
-def device_loader(dataset, batch_size, device, rank=0, world=1, seed=42, pitch_shift=0):
+def device_loader(dataset, batch_size, device, rank=0, world=1, seed=42, pitch_shift=0, acoustics=None):
     """DeviceCorpus over the in-memory tracks of a PianoRollAudioDataset (``dataset.data``); with world > 1 every rank
     keeps a disjoint shard (tracks rank, rank + world, ...) and its own item-order stream -- and, with ``pitch_shift``, its own
-    stream of shifts (seeded from the rank's crop seed)."""
+    stream of shifts and, with ``acoustics``, its own stream of acoustic parameters (both seeded from the rank's crop seed)."""
     return DeviceCorpus(dataset.data, dataset.sequence_length, batch_size, device, seed=seed, rank=rank, world=world,
-                        sampler_seed=rank, pitch_shift=pitch_shift, aug_seed=1000003 + seed)
+                        sampler_seed=rank, pitch_shift=pitch_shift, aug_seed=1000003 + seed, acoustics=acoustics,
+                        acoustics_seed=2000003 + seed)

@@ -19,5 +19,5 @@ def train(spec, resume_iteration, train_on, batch_size, sequence_length, small, 
           learning_rate_decay_steps, learning_rate_decay_rate, alpha, clip_gradient_norm, validation_length, refresh, device,
           epoches, logdir, log, iteration, VAT_start, VAT, XI, eps, reconstruction, graph, fused_optimizer, saving_freq,
           device_feed, model_complexity, model_name, VAT_mode, logging_freq, device_metrics, tune_thresholds, weight_decay,
-          ema_decay, clip_before_step, pitch_shift):
+          ema_decay, clip_before_step, pitch_shift, reverb_rt60, eq_db, noise_db, reverb_taps):
     return run_training('baseline', **locals())
