@@ -10,9 +10,14 @@
  *     every buffer; scratch is passed in as `workspace`, sized by the *_workspace_bytes queries);
  *   - returns 0 on success, <0 on error (-1 bad argument, -2 launch failure, -3 unsupported shape);
  *     `rv_last_error()` returns the text of the last error on the calling thread;
- *   - re-entrant per stream; the ONE piece of process-global mutable state is the weight-gradient plan table written by
+ *   - re-entrant per stream.  Process-global state, all of it: (1) the weight-gradient plan table written by
  *     rv_conv_wgrad_set_plan (configure it once per shape before the first launch of that shape: the shipped plan table does
- *     exactly that; it is not synchronised against concurrent launches of the same shape).
+ *     exactly that; it is not synchronised against concurrent launches of the same shape); (2) the block-tile policy of rv_gemm,
+ *     an atomic that only the test hook rv_debug_set_gemm_big writes (default: 64 x 64 tiles everywhere); (3) the form of the
+ *     local-attention kernels, fixed when the library is LOADED from RV_ATTN_TILE, RV_ATTN_TILE_WIDE, RV_ATTN_WAVES and
+ *     RV_ATTN_WAVES_WIDE (unset: the shipped choice per head shape) and constant afterwards.  Nothing else is read from the
+ *     environment, and nothing at all on a launch path (the experiment knobs of tools/ exist in the lab / ablation builds only:
+ *     reconvat_amd/build.py).
  *
  * Activations are NHWC with an explicit pixel stride `*_ld` (floats between consecutive pixels), so a
  * tensor may be a channel slice of a wider buffer (the decoder's concat buffers).

@@ -1,5 +1,9 @@
 """Build libreconvat_hip.so (gfx950 only) in-tree with hipcc.  No JIT cache: the .so lives next to the
-sources so it travels with the repo snapshot to the GPU box."""
+sources so it travels with the repo snapshot to the GPU box.
+
+Three variants (csrc/common.h, RV_KNOB).  `product` is the library the package loads and the only one build() makes by default: it reads
+no experiment knob from the environment.  `lab` adds the host-side knobs and the prototypes of tools/; `ablation` adds the in-kernel
+timing hooks on top (WRONG results by design).  The two are for tools/ only and load through RECONVAT_HIP_LIB=<path>."""
 import hashlib
 import os
 import subprocess
@@ -9,7 +13,13 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libreconvat_hip.so')
-SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip', 'gemm.hip', 'gemm_bf16x6.hip', 'attn.hip', 'elementwise.hip', 'mel.hip', 'cqt.hip', 'thickstun.hip', 'data.hip', 'acoustics.hip', 'resample.hip', 'eval.hip', 'lstm.hip', 'api.cpp']
+SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip', 'gemm.hip', 'attn.hip', 'elementwise.hip', 'mel.hip', 'cqt.hip', 'thickstun.hip', 'data.hip', 'acoustics.hip', 'resample.hip', 'eval.hip', 'lstm.hip', 'api.cpp']
+# the sources whose host code changes with the variant (RV_KNOB / RV_LAB / RV_ABLATION; tests/test_abi.py checks the list): a variant
+# compiles these and LAB_SOURCES to objects of its own and shares every other object with the product
+VARIANT_SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip']
+LAB_SOURCES = ['gemm_bf16x6.hip']            # prototypes with a negative result: in no product library
+# variant -> (library suffix, object suffix, flags)
+VARIANTS = {'product': ('', '', []), 'lab': ('_lab', '.lab', ['-DRV_LAB']), 'ablation': ('_abl', '.abl', ['-DRV_ABLATION'])}
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
@@ -34,11 +44,17 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src):
-    obj = os.path.join(CSRC, os.path.splitext(src)[0] + '.o')
+def object_path(src, variant):
+    own = src in VARIANT_SOURCES + LAB_SOURCES         # every other source is the same text in every variant: the product's object
+    return os.path.join(CSRC, os.path.splitext(src)[0] + (VARIANTS[variant][1] if own else '') + '.o')
+
+
+def _compile(src, variant='product'):
+    obj = object_path(src, variant)
+    vflags = VARIANTS[variant][2] if src in VARIANT_SOURCES + LAB_SOURCES else []
     path = os.path.join(CSRC, src)
     deps = [path] + [os.path.join(CSRC, n) for n in sorted(os.listdir(CSRC)) if n.endswith('.h')]
-    extra, stale = [], _stale(obj, deps)
+    extra, stale = list(vflags), _stale(obj, deps)
     if src == 'api.cpp':                       # carries the digest of ALL sources: rebuilt whenever any of them changed
         dig = source_digest()
         extra = [f'-DRV_SOURCE_DIGEST="{dig}"']
@@ -53,48 +69,33 @@ def _compile(src):
             sys.stderr.write(r.stderr)
         if src == 'api.cpp':
             with open(obj + '.digest', 'w') as fh:
-                fh.write(extra[0].split('"')[1])
+                fh.write(dig)
     return obj
 
 
-def build(force=False, verbose=False):
+def lib_path(variant='product'):
+    return os.path.join(HERE, f'libreconvat_hip{VARIANTS[variant][0]}.so')
+
+
+def build(force=False, verbose=False, variant='product'):
+    sources = SOURCES + (LAB_SOURCES if variant != 'product' else [])
     if force:
-        for s in SOURCES:
-            o = os.path.join(CSRC, os.path.splitext(s)[0] + '.o')
-            if os.path.exists(o):
-                os.remove(o)
+        for s in sources:
+            if os.path.exists(object_path(s, variant)):
+                os.remove(object_path(s, variant))
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(_compile, SOURCES))
-    if force or _stale(LIB, objs):
-        cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC'] + objs + ['-o', LIB]
+        objs = list(ex.map(lambda s: _compile(s, variant), sources))
+    lib = lib_path(variant)
+    if force or _stale(lib, objs):
+        cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC'] + objs + ['-o', lib]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stderr}')
     if verbose:
-        print('built', LIB)
-    return LIB
-
-
-def build_ablation():
-    """Timing-experiment build (wrong results by design): conv.hip with -DRV_ABLATION so that RV_ABLATE=bits switches parts of
-    the conv / wgrad kernels off.  Lives next to the real library as libreconvat_hip_abl.so; load it with
-    RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_abl.so (tools only -- never the product default)."""
-    build()
-    obj = os.path.join(CSRC, 'conv_abl.o')
-    r = subprocess.run([HIPCC] + FLAGS + ['-DRV_ABLATION', '-c', os.path.join(CSRC, 'conv.hip'), '-o', obj], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr)
-    objs = [os.path.join(CSRC, os.path.splitext(s)[0] + '.o') for s in SOURCES if s != 'conv.hip'] + [obj]
-    lib = os.path.join(HERE, 'libreconvat_hip_abl.so')
-    r = subprocess.run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC'] + objs + ['-o', lib], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr)
-    print('built', lib)
+        print('built', lib)
     return lib
 
 
 if __name__ == '__main__':
-    if '--ablation' in sys.argv:
-        build_ablation()
-    else:
-        build(force='--force' in sys.argv, verbose=True)
+    build(force='--force' in sys.argv, verbose=True,
+          variant='ablation' if '--ablation' in sys.argv else 'lab' if '--lab' in sys.argv else 'product')

@@ -737,14 +737,6 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kv32_k(AttnArgs a) {
     apply32<NW, false>(A5, AT2_A2LD, Yq, ldk, nchunk, a.dk + orow, a.dld, g * dh, dh, a.L - s0);
 }
 
-// 16-byte DMA lanes are legal for every fp32 row (the source needs 4-byte alignment only; a row tail of dh % 4 floats goes 4 bytes per lane).
-// RV_ATTN_V4_ALIGNED=1 restores the round-3 rule (16-byte aligned rows of a multiple of four floats) for A/B runs.
-static bool attn_v4(int dh, long ld, const void* p) {
-    static const int aligned_only = getenv("RV_ATTN_V4_ALIGNED") ? atoi(getenv("RV_ATTN_V4_ALIGNED")) : 0;
-    if (!aligned_only) return true;
-    return (dh % 4) == 0 && (ld % 4) == 0 && (((uintptr_t)p) & 15) == 0;
-}
-
 static int attn_setup(AttnArgs& a, int dh, const char* who) {
     RV_CHECK_ARG(dh >= 1 && dh <= 256, "%s: head dim %d unsupported", who, dh);
     a.dh = dh;
@@ -784,7 +776,9 @@ static AttnForm attn_form(int dh, int L, long max_ld) {
     return f;
 }
 static unsigned attn_view_bytes(int L, long ld, int dh) { return (unsigned)((((long)L - 1) * ld + dh) * 4); }
-static const size_t kAttnMaxLds = 128 * 1024;
+// LDS of a workgroup above which only ONE fits a CU: beyond it the rel^T block moves to registers and the kv pass stages its two windows
+// one after the other (two workgroups per CU again).  Far below the 128 KiB the kernels may be given (attn_setup), so nothing larger is launched.
+static const size_t kAttnOccLds = 78 * 1024;
 
 extern "C" {
 
@@ -795,17 +789,14 @@ int rv_local_attn_fwd(const float* q, const float* k, const float* v, long ld, c
     if (rc != RV_OK) return rc;
     RV_CHECK_ARG(ld >= (long)G * dh, "rv_local_attn_fwd: row stride %ld < G*dh", ld);
     a.q = q; a.k = k; a.v = v; a.ld = ld; a.rel = relT; a.out = out; a.att = att; a.B = B; a.L = L; a.G = G;
-    a.v4 = attn_v4(dh, ld, q) && attn_v4(dh, ld, k) && attn_v4(dh, ld, v);
-    a.dv4 = attn_v4(dh, (long)G * dh, relT);
+    a.v4 = a.dv4 = 1;      // 16-byte DMA lanes are legal for every fp32 row (the source needs 4-byte alignment only; a row tail of dh % 4 floats goes 4 bytes per lane)
     const int ntile = (L + AT_TT - 1) / AT_TT, ldk = a.dhp + 4;
     size_t lds = ((size_t)(AT_TT + 80) * ldk + AT_TT * AT_SLD + AT_TT * AT_A2LD) * sizeof(float);
-    static const int relregs_env = getenv("RV_ATTN_REL_REGS") ? atoi(getenv("RV_ATTN_REL_REGS")) : 1;
-    static const size_t occ_kb = getenv("RV_ATTN_OCC_KB") ? (size_t)atoi(getenv("RV_ATTN_OCC_KB")) : 78;      // (experiment: 50 -> three workgroups per CU at dh = 128)
-    a.rel_regs = relregs_env && lds > occ_kb * 1024;       // the rel^T block would leave room for only one workgroup per CU
+    a.rel_regs = lds > kAttnOccLds;       // the rel^T block would leave room for only one workgroup per CU
     const AttnForm form = attn_form(dh, L, ld > (long)G * dh ? ld : (long)G * dh);
     if (form.tile == 32) {
         size_t lds32 = ((size_t)(AT2_TT + AT2_WINP + 32) * ldk + AT2_TT * AT2_SLD + AT2_TT * AT2_A2LD) * sizeof(float);
-        a.rel_regs = (relregs_env && lds32 > occ_kb * 1024) || lds32 > kAttnMaxLds;
+        a.rel_regs = lds32 > kAttnOccLds;
         if (a.rel_regs) lds32 -= (size_t)32 * ldk * sizeof(float);
         a.qkv_bytes = attn_view_bytes(L, ld, dh);
         a.rel_bytes = attn_view_bytes(AT_W, (long)G * dh, dh);
@@ -833,20 +824,17 @@ int rv_local_attn_bwd(const float* dout, const float* q, const float* k, const f
     RV_CHECK_ARG(ld >= (long)G * dh && dld >= (long)G * dh, "rv_local_attn_bwd: row stride < G*dh");
     a.q = q; a.k = k; a.v = v; a.ld = ld; a.rel = relT; a.att = (float*)att; a.dout = dout;
     a.dq = dq; a.dk = dk; a.dv = dv; a.dld = dld; a.de = de; a.de_in = de; a.B = B; a.L = L; a.G = G;
-    a.v4 = attn_v4(dh, ld, q) && attn_v4(dh, ld, k) && attn_v4(dh, ld, v);
-    a.dv4 = attn_v4(dh, (long)G * dh, relT) && attn_v4(dh, (long)G * dh, dout);
+    a.v4 = a.dv4 = 1;      // (as in the forward)
     const int ntile = (L + AT_TT - 1) / AT_TT, ldk = a.dhp + 4;
     size_t lds1 = ((size_t)(AT_TT + 80) * ldk + AT_TT * AT_SLD + AT_TT * AT_A3LD) * sizeof(float);
-    static const int relregs_env = getenv("RV_ATTN_REL_REGS") ? atoi(getenv("RV_ATTN_REL_REGS")) : 1;
-    static const size_t occ_kb = getenv("RV_ATTN_OCC_KB") ? (size_t)atoi(getenv("RV_ATTN_OCC_KB")) : 78;
-    a.rel_regs = relregs_env && lds1 > occ_kb * 1024;
+    a.rel_regs = lds1 > kAttnOccLds;
     long max_ld = ld > (long)G * dh ? ld : (long)G * dh;
     if (max_ld < (long)G * AT_W) max_ld = (long)G * AT_W;
     const AttnForm form = attn_form(dh, L, max_ld);
     if (form.tile == 32) {
         a.rel_first = a.rel_regs;                      // dq accumulates in the order the 16-frame form uses for this head shape
         size_t q32 = ((size_t)(AT2_TT + AT2_WINP + 32) * ldk + AT2_TT * AT2_SLD + AT2_TT * AT2_A3LD) * sizeof(float);
-        a.rel_regs = (relregs_env && q32 > occ_kb * 1024) || q32 > kAttnMaxLds;
+        a.rel_regs = q32 > kAttnOccLds;
         if (a.rel_regs) q32 -= (size_t)32 * ldk * sizeof(float);
         a.qkv_bytes = attn_view_bytes(L, ld, dh);
         a.do_bytes = attn_view_bytes(L, (long)G * dh, dh);
@@ -857,7 +845,7 @@ int rv_local_attn_bwd(const float* dout, const float* q, const float* k, const f
         else hipLaunchKernelGGL((attn_bwd_q32_k<5>), grid, block, q32, st, a);
         RV_LAUNCH_CHECK("rv_local_attn_bwd(q)");
         const size_t two32 = ((size_t)2 * AT2_WINP * ldk + 2 * AT2_WINP * 32 + 2 * AT2_TT * AT2_A2LD) * sizeof(float);
-        a.seq_kv = two32 > occ_kb * 1024;              // (always so beyond 128 KB: occ_kb is far below)
+        a.seq_kv = two32 > kAttnOccLds;
         const size_t kv32 = two32 - (a.seq_kv ? (size_t)AT2_WINP * ldk * sizeof(float) : 0);
         if (form.waves == 10) hipLaunchKernelGGL((attn_bwd_kv32_k<10>), grid, block, kv32, st, a);
         else hipLaunchKernelGGL((attn_bwd_kv32_k<5>), grid, block, kv32, st, a);
@@ -868,7 +856,7 @@ int rv_local_attn_bwd(const float* dout, const float* q, const float* k, const f
     hipLaunchKernelGGL(attn_bwd_q_k, dim3(B * ntile, G), dim3(AT_NTHR), lds1, st, a);
     RV_LAUNCH_CHECK("rv_local_attn_bwd(q)");
     const size_t lds_two = ((size_t)2 * AT_WINP * ldk + 2 * AT_WINP * 32 + 2 * AT_TT * AT_A2LD) * sizeof(float);
-    a.seq_kv = lds_two > occ_kb * 1024;            // two windows at once would leave room for only one workgroup per CU
+    a.seq_kv = lds_two > kAttnOccLds;            // two windows at once would leave room for only one workgroup per CU
     const size_t lds2 = lds_two - (a.seq_kv ? (size_t)AT_WINP * ldk * sizeof(float) : 0);
     hipLaunchKernelGGL(attn_bwd_kv_k, dim3(B * ntile, G), dim3(AT_NTHR), lds2, st, a);
     RV_LAUNCH_CHECK("rv_local_attn_bwd(kv)");

@@ -366,13 +366,11 @@ __global__ __launch_bounds__(256) void bn_apply_k(BnArgs a) {
 // second round half empty: 3072 -> 1023 is -0.2 ms per step in situ (2046 / 1536 / 1023 / 768 within noise of each other, 510 and
 // 255 slower again: too few loads in flight).  The backward form (two input streams) likes 768 best: 1023 / 768 / 639 / 510 =
 // 22.29 / 22.19 / 22.24 / 22.30 ms per step.  Round 5, with the re-tuned conv table, the forward form likes 768 / 639 better than 1023 as well
-// (tools/knob_ab.sh, 6 interleaved runs each: 21.43 / 21.43 vs 21.52 ms; 510: 21.52) -> 768 for both.  RV_BN_MAXBLK / RV_BN_MAXBLK_BWD override (tuning only).
+// (tools/knob_ab.sh, 6 interleaved runs each: 21.43 / 21.43 vs 21.52 ms; 510: 21.52) -> 768 for both.  RV_BN_MAXBLK / RV_BN_MAXBLK_BWD override (lab build only).
 // Restated in tests/stream_cases.py (bn_apply_blocks, bn_apply_launch: the `fixed` test and trip counts of bn_apply_k): keep the two in step.
 static int bn_apply_blocks(long total, bool bwd = false) {
     long b = (total + 255) / 256;
-    static const long capf = getenv("RV_BN_MAXBLK") ? atol(getenv("RV_BN_MAXBLK")) : 768;
-    static const long capb = getenv("RV_BN_MAXBLK_BWD") ? atol(getenv("RV_BN_MAXBLK_BWD")) : 768;
-    const long cap = bwd ? capb : capf;
+    const long cap = bwd ? RV_KNOB("RV_BN_MAXBLK_BWD", 768) : RV_KNOB("RV_BN_MAXBLK", 768);
     if (b > cap) b = cap;
     b = ((b + 2) / 3) * 3;          // multiple of 3: see bn_apply_k
     return (int)b;

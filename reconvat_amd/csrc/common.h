@@ -33,6 +33,24 @@ extern "C" void rv_set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Host-side experiment knobs.  The product library reads nothing from the environment on a launch path: RV_KNOB("NAME", dflt) is the
+// literal default there, the branches on it fold away and the object has no reference to getenv.  A lab build (-DRV_LAB; the ablation
+// build -DRV_ABLATION implies it and adds the in-kernel hooks) makes it the integer value of the environment variable NAME, read ONCE
+// per use site, on its first evaluation (a function-local static: launches come from the autograd thread as well as the main thread).
+#ifdef RV_ABLATION
+#define RV_LAB 1
+#endif
+#ifdef RV_LAB
+#include <stdlib.h>
+static inline long rv_knob_read(const char* name, long dflt) {
+    const char* e = getenv(name);
+    return e ? atol(e) : dflt;
+}
+#define RV_KNOB(name, dflt) ([]() -> long { static const long v = rv_knob_read(name, dflt); return v; }())
+#else
+#define RV_KNOB(name, dflt) ((long)(dflt))
+#endif
+
 // ---- wave64 reductions -------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

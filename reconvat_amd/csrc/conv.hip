@@ -2711,8 +2711,8 @@ static void choose_tiles(long ntiles, int ntile_n, int* NT, int* MT) {
 }
 
 // LDS-pipelined 3x3 launch: pick (NT, MTW, TH) so that two units fit LDS and the persistent grid covers the chip
-static size_t conv3x3_lds_bytes(int R, int NT, int TH, int W, int nchunk, int nbuf = 2) {
-    return ((size_t)nbuf * (TH + 2) * (W + 2) * 4 * R + (size_t)(nchunk > 1 ? nbuf : 1) * 9 * NT * 64 * R) * sizeof(float);
+static size_t conv3x3_lds_bytes(int R, int NT, int TH, int W, int nchunk) {
+    return ((size_t)2 * (TH + 2) * (W + 2) * 4 * R + (size_t)(nchunk > 1 ? 2 : 1) * 9 * NT * 64 * R) * sizeof(float);
 }
 
 template <int R, int NW, bool BF = false>
@@ -2720,15 +2720,11 @@ static int launch_conv3x3_lds_r(const ConvArgs& a, int NT, int MTW, int TH, int 
     ConvLdsArgs aa;
     aa.c = a; aa.TH = TH;
     dim3 grid(band_grid(aa, NT, 256 * wgs_per_cu)), blk(NW * 64);
-    // RV_CONV_NBUF=3: a third unit buffer (prefetch distance 2) when it fits.  Measured neutral on MI355X (the
-    // kernel is not DMA-latency bound), so two buffers -- less LDS -- stay the default.
-    static const int nbuf_env = getenv("RV_CONV_NBUF") ? atoi(getenv("RV_CONV_NBUF")) : 0;
-    aa.nbuf = 2;
-    if (nbuf_env == 3 && conv3x3_lds_bytes(R, NT, TH, a.W, a.nchunk, 3) <= (size_t)(wgs_per_cu > 1 ? 76 : 150) * 1024) aa.nbuf = 3;
-    aa.ablate = getenv("RV_ABLATE") ? atoi(getenv("RV_ABLATE")) : 0;
-    static const int skew_env = getenv("RV_CONV_SKEW") ? atoi(getenv("RV_CONV_SKEW")) : 1;
-    aa.skew = (aa.nbuf == 3 && NW >= 8) ? skew_env : 0;
-    const size_t lds = conv3x3_lds_bytes(R, NT, TH, a.W, a.nchunk, aa.nbuf);
+    // two unit buffers, no skew: a third buffer (prefetch distance 2) measured neutral on MI355X -- the kernel is not DMA-latency bound --
+    // and costs LDS (the kernel's nbuf == 3 / skew branches are unreachable)
+    aa.nbuf = 2; aa.skew = 0;
+    aa.ablate = RV_ABLATE_MASK();
+    const size_t lds = conv3x3_lds_bytes(R, NT, TH, a.W, a.nchunk);
 #define RV_L3(nt, mt)                                                                              \
     if (NT == nt && MTW == mt) {                                                                  \
         auto kern = conv3x3_lds_k<R, nt, mt, NW, BF>;                                             \
@@ -2818,13 +2814,12 @@ static int launch_conv3x3_lds(const ConvArgs& a, int R, hipStream_t st, int forc
 template <int NW, bool HALF = false>
 static int launch_conv3x3_wino(const ConvArgs& a0, int NT, int MTW, int force_th, hipStream_t st, size_t cap = 154 * 1024, int wg_slots = 256) {
     // weights: resident for the whole kernel when all chunks fit next to the two band buffers, else double-buffered per chunk like the band
-    static const int wres_env = getenv("RV_WINO_WRES") ? atoi(getenv("RV_WINO_WRES")) : 1;
     ConvLdsArgs aa;
     dim3 grid, blk(NW * 64);
     size_t lds;
-    const int rc = wino_band_plan(aa, grid, lds, a0, NT, MTW, NW, force_th, cap, wg_slots, WinoWeightPolicy{2, false, wres_env != 0});
+    const int rc = wino_band_plan(aa, grid, lds, a0, NT, MTW, NW, force_th, cap, wg_slots, WinoWeightPolicy{2, false, true});
     if (rc != RV_OK) return rc;
-    aa.ablate = getenv("RV_ABLATE") ? atoi(getenv("RV_ABLATE")) : 0;
+    aa.ablate = RV_ABLATE_MASK();
 #define RV_WN(nt, mt)                                                                              \
     if (NT == nt && MTW == mt) {                                                                  \
         static std::once_flag attr_once;                                                          \
@@ -2852,7 +2847,8 @@ static int frag_R(int kdim) { return (kdim % 16 == 0) ? 4 : ((kdim % 8 == 0) ? 2
 // 3x3 weights with 16-channel chunks carry their Winograd transform behind the nine tap fragments (conv3x3_wino_k)
 static bool wino_packed(int taps, int kdim) { return taps == 9 && kdim % 16 == 0; }
 
-// ---- profiling aid: raw f32 MFMA issue rate (NACC independent accumulators per wave) -------------------------
+#ifdef RV_LAB
+// ---- profiling aid (lab builds only): raw f32 MFMA issue rate (NACC independent accumulators per wave) -------------------------
 template <int NACC>
 __global__ __launch_bounds__(256) void mfma_peak_k(float* out, int iters, float seed) {
     f32x4 acc[NACC];
@@ -2872,10 +2868,8 @@ __global__ __launch_bounds__(256) void mfma_peak_k(float* out, int iters, float 
     out[blockIdx.x * 256 + threadIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
-extern "C" {
-
-// profiling aid: nacc in {2,4,8}; returns 0.  FLOPs = blocks*4 waves*iters*4*nacc*2048
-int rv_debug_mfma_peak(float* out, int blocks, int iters, int nacc, void* stream) {
+// nacc in {2,4,8}; returns 0.  FLOPs = blocks*4 waves*iters*4*nacc*2048
+extern "C" int rv_debug_mfma_peak(float* out, int blocks, int iters, int nacc, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (nacc == 2) hipLaunchKernelGGL(mfma_peak_k<2>, dim3(blocks), dim3(256), 0, st, out, iters, 1.0f);
     else if (nacc == 4) hipLaunchKernelGGL(mfma_peak_k<4>, dim3(blocks), dim3(256), 0, st, out, iters, 1.0f);
@@ -2883,6 +2877,9 @@ int rv_debug_mfma_peak(float* out, int blocks, int iters, int nacc, void* stream
     RV_LAUNCH_CHECK("rv_debug_mfma_peak");
     return RV_OK;
 }
+#endif
+
+extern "C" {
 
 // Size (floats) of the packed fragment buffer for a logical Wm[taps][kdim][ndim].
 long rv_packed_weight_floats(int taps, int kdim, int ndim) {
@@ -3016,8 +3013,7 @@ static int conv_fwd_impl(int mode, const float* in, int in_ld, int B, int H, int
 #define RV_NARROW(ci, co)                                                                         \
     if (mode == 0 && Cin == ci && Cout == co && (in_ld & 3) == 0 && ((((uintptr_t)in) & 15) == 0)) { \
         RV_CHECK_ARG(s.npix < (1L << 28), "rv_conv_fwd: more than 2^28 pixels");                \
-        static const int nrows_env = getenv("RV_NARROW_ROWS") ? atoi(getenv("RV_NARROW_ROWS")) : 16;   \
-        s.rows = nrows_env;                                                                      \
+        s.rows = 16;                                                                             \
         const long nb = (long)B * cdiv(H, s.rows) * cdiv(W, 256 / (ci / 4));                     \
         hipLaunchKernelGGL((conv_narrow_out_k<ci, co>), dim3((unsigned)nb), blk, 0, st, s);      \
         RV_LAUNCH_CHECK("conv_narrow_out");                                                      \
@@ -3025,10 +3021,9 @@ static int conv_fwd_impl(int mode, const float* in, int in_ld, int B, int H, int
     }
         RV_NARROW(16, 1) RV_NARROW(8, 2) RV_NARROW(8, 1)
 #undef RV_NARROW
-        static const int cin1_env = getenv("RV_CONV_CIN1") ? atoi(getenv("RV_CONV_CIN1")) : 1;
         const bool cin12 = mode == 0 && ((Cin == 1 && (Cout == 16 || Cout == 8)) || (Cin == 2 && Cout == 8 && (in_ld & 1) == 0 && ((((uintptr_t)in) & 7) == 0)));
         const bool bz_ok = !bn.z || ((bn.z_ld & 3) == 0 && ((((uintptr_t)bn.z) & 15) == 0) && ((((uintptr_t)bn.coef) & 15) == 0));
-        if (cin1_env && cin12 && bz_ok && (!bias || ((((uintptr_t)bias) & 15) == 0))) {
+        if (cin12 && bz_ok && (!bias || ((((uintptr_t)bias) & 15) == 0))) {
             s.rows = 16;
             s.bn_z = bn.z; s.bn_z_ld = bn.z_ld; s.bn_coef = bn.coef; s.bn_slope = bn.slope;
             if (bn.z) { s.bn_sums = bn_sums; *sums_done = true; }      // the backward reduction rides in this kernel's epilogue
@@ -3170,7 +3165,7 @@ static WgradPlan wgrad_plan(int taps, int B, int Hv, int Ca, int Cb) {
     p.small = (Ca * Cb * taps <= 144) && (Ca < 8 || Cb < 8);
     if (p.small) {
         p.TA = p.TB = p.nga = p.ngb = 1; p.rows_per_wave = 0;
-        { static int np = getenv("RV_WGS_NPARTS") ? atoi(getenv("RV_WGS_NPARTS")) : 4096; p.nparts = nrows < np ? nrows : np; }
+        p.nparts = nrows < 4096 ? nrows : 4096;
         return p;
     }
     // channel-group shape (TA x TB tiles of 16): the one that pads the channel counts least (48 = 3 x 16, not 2 x 32);
@@ -3183,9 +3178,7 @@ static WgradPlan wgrad_plan(int taps, int B, int Hv, int Ca, int Cb) {
             if (best < 0 || padded < best) { best = padded; p.TA = ta; p.TB = tb; }
         }
     p.nga = cdiv(Ca, p.TA * 16); p.ngb = cdiv(Cb, p.TB * 16);
-    static int want_total = 0;
-    if (!want_total) { const char* e = getenv("RV_WGRAD_WGS"); want_total = e ? atoi(e) : 256; }
-    int total = want_total;
+    int total = (int)RV_KNOB("RV_WGRAD_WGS", 256);      // workgroups on the chip (lab: tools/sweep_wgrad.sh)
     p.wino = false;
     if (const WgradTune* t = wgrad_tuned(taps, B, Hv, Ca, Cb)) {
         if (t->wgs > 0) total = t->wgs;
@@ -3289,9 +3282,8 @@ long rv_wgrad_table_finalize(void* table_host, int count) {
 int rv_wgrad_reduce_table(const void* table_dev, int count, long total_blocks, void* stream) {
     if (count <= 0 || total_blocks <= 0) return RV_OK;
     RV_CHECK_ARG(table_dev, "rv_wgrad_reduce_table: null table");
-    static const int plain = getenv("RV_ABL_WREDUCE_PLAIN") ? atoi(getenv("RV_ABL_WREDUCE_PLAIN")) : 0;      // (ablation build only)
     hipLaunchKernelGGL(wgrad_reduce_table_k, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const WreduceEntry*)table_dev, count, plain);
+                       (const WreduceEntry*)table_dev, count, 0);
     RV_LAUNCH_CHECK("rv_wgrad_reduce_table");
     return RV_OK;
 }
@@ -3324,8 +3316,8 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
     a.B = B; a.want_bias = dbias != nullptr;
     a.nseg = nseg; a.Bseg = B / nseg;
     for (int i = 0; i < 4; ++i) { a.Useg[i] = nseg > 1 ? Useg[i < nseg ? i : 0] : U; a.Vseg[i] = nseg > 1 ? Vseg[i < nseg ? i : 0] : V; }
-    a.ablate = getenv("RV_ABLATE") ? atoi(getenv("RV_ABLATE")) : 0;
-    a.dbg = getenv("RV_DBG_PTR") ? (unsigned long long*)strtoull(getenv("RV_DBG_PTR"), nullptr, 10) : nullptr;
+    a.ablate = RV_ABLATE_MASK();
+    a.dbg = rv_dbg_ptr();
     a.pstride = (long)taps * Ca * Cb + Cb;
     a.fd_vplane = fastdiv_make((unsigned)(Hv * Wv)); a.fd_wv = fastdiv_make((unsigned)Wv);
     RV_CHECK_ARG((long)B * Hv * Wv < (1L << 31), "rv_conv_wgrad: more than 2^31 pixels");
@@ -3363,33 +3355,27 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
     }
         if (mode == 0 && Ca == 8 && (Cb == 1 || Cb == 2) && (u_ld & 3) == 0 && ((((uintptr_t)U) & 15) == 0) && Hu == Hv && Wu == Wv) {
             // sliding-window kernel: one partial per wave = (image, band of `rows` rows, strip of 32 columns)
-            static const int sw_env = getenv("RV_WGRAD_SW") ? atoi(getenv("RV_WGRAD_SW")) : 1;
-            if (sw_env) {
-                const int nstrip = cdiv(Wv, 32);
-                int rows = 16;
-                while (rows < Hv && (long)B * cdiv(Hv, rows) * nstrip > plan.nparts) rows *= 2;   // the workspace holds plan.nparts partials
-                const int nband = cdiv(Hv, rows);
-                if ((long)B * nband * nstrip <= plan.nparts) {          // (tiny images: the flat kernel below)
-                    a.nparts = B * nband * nstrip;
-                    dim3 g2(cdiv(a.nparts, 4));
-                    if (Cb == 2) hipLaunchKernelGGL((wgrad_small_sw_k<2>), g2, blk, 0, st, a, rows, nstrip, nband);
-                    else hipLaunchKernelGGL((wgrad_small_sw_k<1>), g2, blk, 0, st, a, rows, nstrip, nband);
-                    goto reduce;
-                }
+            const int nstrip = cdiv(Wv, 32);
+            int rows = 16;
+            while (rows < Hv && (long)B * cdiv(Hv, rows) * nstrip > plan.nparts) rows *= 2;   // the workspace holds plan.nparts partials
+            const int nband = cdiv(Hv, rows);
+            if ((long)B * nband * nstrip <= plan.nparts) {          // (tiny images: the flat kernel below)
+                a.nparts = B * nband * nstrip;
+                dim3 g2(cdiv(a.nparts, 4));
+                if (Cb == 2) hipLaunchKernelGGL((wgrad_small_sw_k<2>), g2, blk, 0, st, a, rows, nstrip, nband);
+                else hipLaunchKernelGGL((wgrad_small_sw_k<1>), g2, blk, 0, st, a, rows, nstrip, nband);
+                goto reduce;
             }
         }
         if (mode == 0 && Ca == 1 && Cb == 16 && (v_ld & 3) == 0 && ((((uintptr_t)V) & 15) == 0) && Hu == Hv && Wu == Wv) {
-            static const int c1_env = getenv("RV_WGRAD_SW") ? atoi(getenv("RV_WGRAD_SW")) : 1;
-            if (c1_env) {
-                const int nstrip = cdiv(Wv, 16);
-                int rows = 32;
-                while (rows < Hv && (long)B * cdiv(Hv, rows) * nstrip > plan.nparts) rows *= 2;
-                const int nband = cdiv(Hv, rows);
-                if ((long)B * nband * nstrip <= plan.nparts) {
-                    a.nparts = B * nband * nstrip;
-                    hipLaunchKernelGGL(wgrad_cin1_k, dim3(cdiv(a.nparts, 4)), blk, 0, st, a, rows, nstrip, nband);
-                    goto reduce;
-                }
+            const int nstrip = cdiv(Wv, 16);
+            int rows = 32;
+            while (rows < Hv && (long)B * cdiv(Hv, rows) * nstrip > plan.nparts) rows *= 2;
+            const int nband = cdiv(Hv, rows);
+            if ((long)B * nband * nstrip <= plan.nparts) {
+                a.nparts = B * nband * nstrip;
+                hipLaunchKernelGGL(wgrad_cin1_k, dim3(cdiv(a.nparts, 4)), blk, 0, st, a, rows, nstrip, nband);
+                goto reduce;
             }
         }
         if (mode == 0) { RV_WS(1, 16, 3, 3, 1, 1) RV_WS(8, 2, 3, 3, 1, 1) RV_WS(8, 1, 3, 3, 1, 1) }
@@ -3410,9 +3396,7 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
             bf = false; Wv4 = (Wv + 3) & ~3; UP = SS * (Wv4 - 1) + KH;
             lds = ((size_t)nslot * UP * TA * 16 + (size_t)2 * Wv4 * TB * 16) * sizeof(float);
         }
-        static int nw_env = 0;
-        if (!nw_env) { const char* e = getenv("RV_WGRAD_NW"); nw_env = (e && atoi(e) == 4) ? 4 : 8; }
-        const int nw = plan.nw ? plan.nw : nw_env;
+        const int nw = plan.nw ? plan.nw : (RV_KNOB("RV_WGRAD_NW", 8) == 4 ? 4 : 8);      // (lab: tools/sweep_wgrad.sh)
         // fold tree: (x groups / 2) slots per tile half, each [taps * TAW * TB + TB] accumulators x 64 lanes
         const int nh_ = (nw == 8 && TA == 2 && TB == 2) ? 2 : 1, nxg_ = nw / nh_;
         const size_t fold = (size_t)nh_ * (nxg_ / 2) * ((mode == 0 ? 9 : (mode == 1 ? 1 : 4)) * (TA / nh_) * TB + TB) * 4 * 64 * sizeof(float);
@@ -3480,37 +3464,28 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
     }
 reduce:
     RV_LAUNCH_CHECK("rv_conv_wgrad");
-#ifdef RV_ABLATION
-    static const int skip_reduce = getenv("RV_ABL_SKIP_WREDUCE") ? atoi(getenv("RV_ABL_SKIP_WREDUCE")) : 0;   // timing ablation (wrong results)
-#else
-    const int skip_reduce = 0;
-#endif
-    if (!skip_reduce) {
-        WreduceArgs r;
-        r.part = a.part; r.pstride = a.pstride; r.nparts = a.nparts; r.taps = taps; r.Ca = Ca; r.Cb = Cb;
-        r.dw = dw; r.s_a = s_a; r.s_b = s_b; r.flip = flip; r.dbias = dbias; r.accumulate = accumulate;
-        long nel = (long)taps * Ca * Cb + (dbias ? Cb : 0);
-        const int el = (cdiv(nel, 64) >= 256 || a.nparts <= 8) ? 64 : ((cdiv(nel, 16) >= 256 || a.nparts <= 32) ? 16 : 4);
-        static const int v4_env = getenv("RV_WREDUCE_V4") ? atoi(getenv("RV_WREDUCE_V4")) : 1;
-        const int vec4 = v4_env && el >= 16 && (nel & 3) == 0 && (a.pstride & 3) == 0 && (((uintptr_t)a.part) & 15) == 0;
-        // deferred (table) form of a large gradient: 1024 elements per workgroup, every thread walks ALL partials of its four elements
-        // -- 4 KiB contiguous per partial and workgroup instead of 256-byte pieces at partial stride; the table's other entries fill the chip
-        static const int wide_env = getenv("RV_WREDUCE_WIDE") ? atoi(getenv("RV_WREDUCE_WIDE")) : 1;
-        if (defer && vec4 && wide_env && nel >= 8192) {
-            defer->a = r; defer->block0 = cdiv(nel, 1024); defer->el = 1024; defer->vec4 = 1;
-            return RV_OK;
-        }
-        if (defer) {
-            defer->a = r; defer->block0 = cdiv(nel, el); defer->el = el; defer->vec4 = vec4;
-            return RV_OK;
-        }
-        if (vec4 && el == 64) hipLaunchKernelGGL((wgrad_reduce_k<64, true>), dim3(cdiv(nel, 64)), dim3(256), 0, st, r);
-        else if (vec4 && el == 16) hipLaunchKernelGGL((wgrad_reduce_k<16, true>), dim3(cdiv(nel, 16)), dim3(256), 0, st, r);
-        else if (el == 64) hipLaunchKernelGGL(wgrad_reduce_k<64>, dim3(cdiv(nel, 64)), dim3(256), 0, st, r);
-        else if (el == 16) hipLaunchKernelGGL(wgrad_reduce_k<16>, dim3(cdiv(nel, 16)), dim3(256), 0, st, r);
-        else hipLaunchKernelGGL(wgrad_reduce_k<4>, dim3(cdiv(nel, 4)), dim3(256), 0, st, r);
-        RV_LAUNCH_CHECK("rv_conv_wgrad(reduce)");
+    WreduceArgs r;
+    r.part = a.part; r.pstride = a.pstride; r.nparts = a.nparts; r.taps = taps; r.Ca = Ca; r.Cb = Cb;
+    r.dw = dw; r.s_a = s_a; r.s_b = s_b; r.flip = flip; r.dbias = dbias; r.accumulate = accumulate;
+    long nel = (long)taps * Ca * Cb + (dbias ? Cb : 0);
+    const int el = (cdiv(nel, 64) >= 256 || a.nparts <= 8) ? 64 : ((cdiv(nel, 16) >= 256 || a.nparts <= 32) ? 16 : 4);
+    const int vec4 = el >= 16 && (nel & 3) == 0 && (a.pstride & 3) == 0 && (((uintptr_t)a.part) & 15) == 0;
+    // deferred (table) form of a large gradient: 1024 elements per workgroup, every thread walks ALL partials of its four elements
+    // -- 4 KiB contiguous per partial and workgroup instead of 256-byte pieces at partial stride; the table's other entries fill the chip
+    if (defer && vec4 && nel >= 8192) {
+        defer->a = r; defer->block0 = cdiv(nel, 1024); defer->el = 1024; defer->vec4 = 1;
+        return RV_OK;
     }
+    if (defer) {
+        defer->a = r; defer->block0 = cdiv(nel, el); defer->el = el; defer->vec4 = vec4;
+        return RV_OK;
+    }
+    if (vec4 && el == 64) hipLaunchKernelGGL((wgrad_reduce_k<64, true>), dim3(cdiv(nel, 64)), dim3(256), 0, st, r);
+    else if (vec4 && el == 16) hipLaunchKernelGGL((wgrad_reduce_k<16, true>), dim3(cdiv(nel, 16)), dim3(256), 0, st, r);
+    else if (el == 64) hipLaunchKernelGGL(wgrad_reduce_k<64>, dim3(cdiv(nel, 64)), dim3(256), 0, st, r);
+    else if (el == 16) hipLaunchKernelGGL(wgrad_reduce_k<16>, dim3(cdiv(nel, 16)), dim3(256), 0, st, r);
+    else hipLaunchKernelGGL(wgrad_reduce_k<4>, dim3(cdiv(nel, 4)), dim3(256), 0, st, r);
+    RV_LAUNCH_CHECK("rv_conv_wgrad(reduce)");
     return RV_OK;
 }
 

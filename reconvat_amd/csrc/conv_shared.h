@@ -26,10 +26,20 @@ template <int R> struct VecR;
 template <> struct VecR<4> { typedef f32x4 T; };
 template <> struct VecR<2> { typedef f32x2 T; };
 
+// Ablation build (-DRV_ABLATION; timing experiments, wrong results): the kernels honour the `ablate` / `dbg` fields of their arguments,
+// which the launchers fill from RV_ABLATE (a bit mask) and RV_DBG_PTR (a device pointer for the s_memtime stamps), each read once.
+// Every other build passes 0 / null.
 #ifdef RV_ABLATION
 #define ABL(aa) ((aa).ablate)
+#define RV_ABLATE_MASK() ((int)RV_KNOB("RV_ABLATE", 0))
+static inline unsigned long long* rv_dbg_ptr() {
+    static unsigned long long* const p = getenv("RV_DBG_PTR") ? (unsigned long long*)strtoull(getenv("RV_DBG_PTR"), nullptr, 10) : nullptr;
+    return p;
+}
 #else
 #define ABL(aa) 0
+#define RV_ABLATE_MASK() 0
+static inline unsigned long long* rv_dbg_ptr() { return nullptr; }
 #endif
 struct ConvLdsArgs {
     ConvArgs c;

@@ -23,7 +23,7 @@
 #define RV_W2_SIDE 2
 #endif
 
-// AB: timing ablations (wrong results by design; instantiated only in -DRV_W2_DEV builds, selected with RV_W2_ABL=mask):
+// AB: timing ablations (wrong results by design; instantiated only in the ablation build, -DRV_ABLATION, selected with RV_W2_ABL=mask):
 //   1 no MFMAs | 2 no patch reads / transforms | 4 no weight-fragment reads | 8 no unit barrier | 16 no staging after the prologue |
 //   32 no band epilogue | 64 no statistics tail
 template <int NT, int MTW, int NW, bool HALF, bool BNZ, int AB = 0>
@@ -470,11 +470,10 @@ int rv_launch_conv3x3_wino2(const ConvArgs& a0, int NT, int MTW, int nw, int hal
     // (instantiated: the tiles that fit the register file without scratch; the 8-wave NT = 2 tile does not carry the fused
     // BatchNorm-backward epilogue -- refused, like the 12-wave tile of conv3x3_wino_k)
     if (nw == 8 && half && NT == 2 && a0.bn_z) return RV_EUNSUPPORTED;
-#ifdef RV_W2_DEV
-    if (const char* e = getenv("RV_W2_ABL")) {
-        const int mask = atoi(e);
+#ifdef RV_ABLATION
+    if (const int mask = (int)RV_KNOB("RV_W2_ABL", 0)) {      // (read once: tools/w2_ablate.py starts one process per mask)
         if (NT == 1 && MTW == 1 && nw == 8 && !half && !a0.bn_z) {
-#define RV_W2A(m) if (mask == m) { hipFuncSetAttribute((const void*)conv3x3_wino2_k<1, 1, 8, false, false, m>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); \
+#define RV_W2A(m) if (mask == m) { (void)hipFuncSetAttribute((const void*)conv3x3_wino2_k<1, 1, 8, false, false, m>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024); \
             hipLaunchKernelGGL((conv3x3_wino2_k<1, 1, 8, false, false, m>), grid, dim3(512), lds, st, aa); return RV_OK; }
             RV_W2A(126) RV_W2A(122) RV_W2A(120) RV_W2A(96) RV_W2A(64) RV_W2A(1) RV_W2A(2) RV_W2A(26) RV_W2A(24) RV_W2A(30) RV_W2A(124) RV_W2A(32)
 #undef RV_W2A

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void gemm_mfma_k(GemmArgs a) {
 // double-buffered LDS tile (ONE barrier per 32 k).  No split-K / batch / row sums / second destination: rv_gemm routes those to gemm_mfma_k.
 // MEASURED (tools/bench_gemm_big.py, profiles/r06_gemm_big_tiles.txt): bit-identical on every shape and SLOWER on 13 of 15 (x0.56 .. x1.00; 5120 x 1536 x 768:
 // 127 vs 139 us is the one win) -- thousands of small workgroups at 6-8 per CU hide the load -> LDS -> MFMA chain better than 2-3 large ones; the operand-traffic
-// reading of the bf16x6 ladder was wrong.  Kept as an opt-in policy (RV_GEMM_BIG=1 / rv_debug_set_gemm_big) so that the table can be re-measured; default off.
+// reading of the bf16x6 ladder was wrong.  Kept as an opt-in policy (rv_debug_set_gemm_big) so that the table can be re-measured; default off.
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void gemm_big_k(GemmArgs a) {
     constexpr int TY = BM / 32, TX = BN / 32;            // 16 x 16 tiles per wave along m / n (wave grid 2 x 2)
@@ -406,25 +406,13 @@ __global__ void zero_strided_k(float* c, long scm, long scn, int M, int N) {
 }
 
 // block-tile policy of rv_gemm (see gemm_big_k): 0 = always 64 x 64 (DEFAULT: profiles/r06_gemm_big_tiles.txt -- the larger tiles are bit-identical and
-// slower on 13 of 15 shapes), 1 = automatic (RV_GEMM_BIG=1), 2 / 3 = force 128 x 128 / 128 x 64
-static std::atomic<int> g_gemm_big{-1};
-static int gemm_big_mode() {
-    int m = g_gemm_big.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = getenv("RV_GEMM_BIG") ? atoi(getenv("RV_GEMM_BIG")) : 0;
-        g_gemm_big.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// slower on 13 of 15 shapes), 1 = automatic, 2 / 3 = force 128 x 128 / 128 x 64.  Set by rv_debug_set_gemm_big only.
+static std::atomic<int> g_gemm_big{0};
 
 extern "C" {
 
 // experiment / test hook (not part of include/reconvat_hip.h): set the block-tile policy, returns the previous one
-int rv_debug_set_gemm_big(int mode) {
-    const int prev = gemm_big_mode();
-    g_gemm_big.store(mode, std::memory_order_relaxed);
-    return prev;
-}
+int rv_debug_set_gemm_big(int mode) { return g_gemm_big.exchange(mode, std::memory_order_relaxed); }
 
 // C[m*scm + n*scn] (+)= act(sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] + bias[n]);  act: 0 none, 1 sigmoid.
 // splitk > 1 splits the reduction over extra workgroups.  With splitk_ws == NULL the slices accumulate by fp32 atomics (C zeroed
@@ -461,11 +449,10 @@ static int gemm_args_make(GemmArgs& a, const float* A, long sam, long sak, const
     a.part = (float*)splitk_ws; a.tickets = (int*)splitk_tickets; a.atomic_out = 0;
     a.rs_part = (splitk > 1 && splitk_ws) ? (float*)splitk_ws + (long)batch * splitk * cdiv(M, GBM) * cdiv(N, GBN) * (4 * 256 * 4) : nullptr;
     const bool a_kfast = (sak <= sam), b_kfast = (sbk <= sbn);
-    // 16-byte loads need a unit stride along the fast dimension, a 16-byte multiple along the slow one and an
-    // aligned base; K-split offsets are multiples of GBK so they preserve alignment
-    static const int uvec_env = getenv("RV_GEMM_UNALIGNED_VEC") ? atoi(getenv("RV_GEMM_UNALIGNED_VEC")) : 1;
-    a.a_vec = ((a_kfast ? sak : sam) == 1) && (uvec_env || ((((a_kfast ? sam : sak) & 3) == 0) && ((((uintptr_t)A) & 15) == 0) && (batch == 1 || (bsa & 3) == 0)));
-    a.b_vec = ((b_kfast ? sbk : sbn) == 1) && (uvec_env || ((((b_kfast ? sbn : sbk) & 3) == 0) && ((((uintptr_t)B) & 15) == 0) && (batch == 1 || (bsb & 3) == 0)));
+    // 16-byte (dwordx4) loads need a unit stride along the fast dimension and nothing else: no 16-byte alignment is demanded of the
+    // base or of the slow stride
+    a.a_vec = (a_kfast ? sak : sam) == 1;
+    a.b_vec = (b_kfast ? sbk : sbn) == 1;
     return RV_OK;
 }
 
@@ -485,8 +472,8 @@ int rv_gemm(const float* A, long sam, long sak, const float* B, long sbk, long s
     }
     dim3 grid(cdiv(N, GBN), cdiv(M, GBM), splitk * batch);
     // larger block tiles for the plain k-contiguous problems (bit-identical sums, see gemm_big_k): the largest tile that still leaves >= 2 workgroups per CU
-    // (>= 1.5 for 128 x 64) -- a short grid of big tiles loses more to the tail than it gains in operand traffic.  RV_GEMM_BIG=0: always 64 x 64.
-    const int big_env = gemm_big_mode();
+    // (>= 1.5 for 128 x 64) -- a short grid of big tiles loses more to the tail than it gains in operand traffic.  Policy 0 (the default): always 64 x 64.
+    const int big_env = g_gemm_big.load(std::memory_order_relaxed);
     if (big_env && a_kfast && b_kfast && splitk == 1 && batch == 1 && !a_rowsum && !C2 && sak == 1 && sbk == 1 && scn == 1 && M >= 128) {
         const long wg128 = (long)cdiv(M, 128) * cdiv(N, 128), wg64 = (long)cdiv(M, 128) * cdiv(N, 64);
         const int force = big_env > 1 ? big_env : 0;              // (2: force 128 x 128, 3: force 128 x 64 -- tests / A-B runs)

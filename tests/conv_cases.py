@@ -510,7 +510,7 @@ for (_ci, _co), _big in _CIN12_BIG.items():
 
 # 6. conv_small_k.  From the kernel text: (a) the 16-byte loads of the CIN % 4 == 0 form are plain `*reinterpret_cast<const f32x4*>(src + c)`
 # global loads of an address that is 4-byte aligned for any in_ld -- the unaligned 16-byte global loads rv_gemm already issues for its odd leading
-# dimensions (RV_GEMM_UNALIGNED_VEC); (b) every tap address is `centre + (cy * W + cx) * in_ld` with cy, cx clamped into [0, H) x [0, W) and at most CIN
+# dimensions (gemm.hip: f32x4u); (b) every tap address is `centre + (cy * W + cx) * in_ld` with cy, cx clamped into [0, H) x [0, W) and at most CIN
 # floats read from it, so every load lies inside the view; out-of-image taps are zeroed by a select afterwards.
 _SMALL_BIG = (2, 17, 65)            # 2210 px: 34 full waves and one of 34 lanes
 # the fallbacks behind conv_narrow_out_k (in_ld = Cin + 1) and conv_cin12_k (in_ld = 3 for 2 -> 8; a bias 4 bytes off a 16-byte boundary for 1 -> 16, 1 -> 8)

@@ -77,7 +77,7 @@ def gemm_regime(M, N, K, sam, sak, sbk, sbn, scm, scn, c2=False, bias=False, act
     if table:
         c2, act, accumulate = False, 0, 1
     a_kfast, b_kfast = sak <= sam, sbk <= sbn                        # (a tie counts as k-fast)
-    a_vec = (sak if a_kfast else sam) == 1                           # RV_GEMM_UNALIGNED_VEC defaults to 1: no alignment demanded
+    a_vec = (sak if a_kfast else sam) == 1                           # unit stride along the fast dimension is all it takes: no alignment demanded
     b_vec = (sbk if b_kfast else sbn) == 1
     kper, sl = kslices(K, splitk)
     live = [(k0, k1) for k0, k1 in sl if k0 < k1]

@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # timing ablations of wgrad_mfma_k (RV_ABLATION build; kernel durations from rocprofv3 --kernel-trace --stats)
 export RECONVAT_HIP_LIB=$GRAFT_REPO_ROOT/reconvat_amd/libreconvat_hip_abl.so
 cd /tmp && export TMPDIR=/tmp

@@ -1,10 +1,12 @@
 """bf16x6 GEMM prototype (reconvat_amd/csrc/gemm_bf16x6.hip, rv_debug_gemm_bf16x6) against the shipped exact-f32 kernel (rv_gemm) on the
 k-contiguous GEMM shapes of the training step: microseconds per launch (hipGraph of 20 launches, rotating operand sets) and the error of
-both against an fp64 product.   python tools/bench_bf16x6.py > profiles/r06_bf16x6_gemm.txt"""
+both against an fp64 product.   python tools/bench_bf16x6.py > profiles/r06_bf16x6_gemm.txt
+Library: the lab build, reconvat_amd/libreconvat_hip_lab.so (python -m reconvat_amd.build --lab) -- the prototype is in no product library."""
 import ctypes
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault('RECONVAT_HIP_LIB', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'reconvat_amd', 'libreconvat_hip_lab.so'))
 import torch
 from reconvat_amd import ops, _lib
 

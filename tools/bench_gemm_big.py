@@ -34,7 +34,7 @@ def timeit(launch):
     return sorted(ts)[2]
 
 
-print('# M x N x K (unsplit, both operands k-contiguous, bias + sigmoid epilogue): us per launch by block tile; "auto" = the size-based policy (RV_GEMM_BIG=1; the shipped default is 64 x 64 everywhere); results compared bit for bit')
+print('# M x N x K (unsplit, both operands k-contiguous, bias + sigmoid epilogue): us per launch by block tile; "auto" = the size-based policy (rv_debug_set_gemm_big(1); the shipped default is 64 x 64 everywhere); results compared bit for bit')
 for m, n, k in SHAPES:
     torch.manual_seed(m + n + k)
     A = [torch.randn(m, k, device=dev) for _ in range(NSET)]

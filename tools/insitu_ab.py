@@ -5,6 +5,8 @@ inverted under the two-stream schedule, so a variant is only
     python tools/insitu_ab.py [--reps 3] name=table.json[,lib.so] name2=...      ('-' = the committed table / the product library)
 
 e.g.  python tools/insitu_ab.py committed=- new=gpurun_out/tuned_plans.json old_lib=-,reconvat_amd/libreconvat_hip_old.so
+A library variant must carry the source digest of the tree it runs in (bench.py refuses any other): link the other build's objects with an
+api.o compiled from this tree (-DRV_SOURCE_DIGEST, reconvat_amd/build.py), as profiles/product_lab_ab.txt did for the parent commit.
 Prints every run and, per variant, min / median ms per step.  Each run is a fresh child process (bench.py without its roofline,
 parity and CPU legs).
 """

@@ -1,9 +1,10 @@
 """Raw f32 MFMA issue rate of the chip (rv_debug_mfma_peak: NACC independent accumulators per wave, no memory traffic): the 146-156 TFLOP/s the
-conv kernels are graded against."""
+conv kernels are graded against.
+Library: the lab build, reconvat_amd/libreconvat_hip_lab.so (python -m reconvat_amd.build --lab) -- the product library has no such symbol."""
 import ctypes, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from reconvat_amd import _lib
-lib = ctypes.CDLL(_lib.LIB_PATH)
+from reconvat_amd import build
+lib = ctypes.CDLL(os.environ.get('RECONVAT_HIP_LIB') or build.lib_path('lab'))
 fn = lib.rv_debug_mfma_peak
 fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
 out = torch.empty(4096 * 256, device='cuda')

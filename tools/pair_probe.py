@@ -9,13 +9,15 @@ hidden = 1: the shorter kernel disappears behind the longer one (perfect co-runn
 
     python tools/pair_probe.py            # the built-in list (persistent Winograd convs at 171 / 230 / 146 / 190 VGPRs against BatchNorm,
                                           # 1x1 conv, attention, GEMM, and against a second conv)
-Kernel specs: conv:<cin>:<cout>:<H>:<W>:<algo hex> | bn:<C>:<H>:<W> | c1:<cin>:<cout>:<H>:<W> | attn | gemm:<M>:<N>:<K>
+Kernel specs: conv:<cin>:<cout>:<H>:<W>:<algo hex> | bn:<C>:<H>:<W> | c1:<cin>:<cout>:<H>:<W> | attn | gemm:<M>:<N>:<K> | mfma:<wgs>:<iters>:<nacc>
+Library: the product library; the mfma specs (the MFMA-issue sets) take rv_debug_mfma_peak from the lab build next to it,
+reconvat_amd/libreconvat_hip_lab.so (python -m reconvat_amd.build --lab).
 """
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from reconvat_amd import ops, _lib
+from reconvat_amd import ops, _lib, build
 
 dev = torch.device('cuda:0')
 B = 8
@@ -91,7 +93,7 @@ def make(spec, tag):
         # MFMA-bound partner (if THIS does not hide a bandwidth-bound kernel, nothing will)
         import ctypes
         blocks, iters, nacc = int(p[1]), int(p[2]), int(p[3])
-        fn = ctypes.CDLL(_lib.LIB_PATH).rv_debug_mfma_peak
+        fn = ctypes.CDLL(build.lib_path('lab')).rv_debug_mfma_peak
         fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         out = torch.empty(4096 * 256, device=dev)
 

@@ -1,8 +1,10 @@
-"""s_memtime stamps of wgrad_mfma_k (RV_ABLATION build): where one workgroup's time goes.
-    RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_abl.so python tools/stamp_wgrad.py c3 32 32 320 114"""
+"""s_memtime stamps of wgrad_mfma_k: where one workgroup's time goes.    python tools/stamp_wgrad.py c3 32 32 320 114
+Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation), which reads RV_DBG_PTR once,
+at its first weight-gradient launch."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault('RECONVAT_HIP_LIB', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'reconvat_amd', 'libreconvat_hip_abl.so'))
 import torch
 dev = torch.device('cuda:0')
 dbg = torch.zeros(64, dtype=torch.int64, device=dev)

@@ -1,6 +1,8 @@
 #!/bin/bash
 # wgrad_mfma_k partitioning sweep: waves per workgroup (RV_WGRAD_NW) x workgroups on the chip (RV_WGRAD_WGS); kernel
 # durations from rocprofv3 --kernel-trace --stats
+# Library: the lab build, reconvat_amd/libreconvat_hip_lab.so (python -m reconvat_amd.build --lab): the product kernels plus the host knobs.
+export RECONVAT_HIP_LIB="$(cd "$(dirname "$0")/.." && pwd)/reconvat_amd/libreconvat_hip_lab.so"
 cd /tmp && export TMPDIR=/tmp
 for cfg in "wgrad c3 32 32 320 114" "wgrad c3 64 64 160 57" "wgrad c3 128 128 80 28" "wgrad c3 16 16 640 229" "wgrad c3 96 48 160 57"; do
   for knobs in "8 256" "4 256" "4 512" "8 512" "4 768" "4 1024"; do

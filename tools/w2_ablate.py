@@ -1,13 +1,13 @@
-"""Timing ablations of the software-pipelined Winograd kernel (conv_wino2.hip, -DRV_W2_DEV build loaded through RECONVAT_HIP_LIB):
-every mask of RV_W2_ABL on a few BASELINE shapes (B = 8, fused statistics).  Results are WRONG by design for mask != 0.
-
-    RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_dev.so python tools/w2_ablate.py
-"""
+"""Timing ablations of the software-pipelined Winograd kernel (conv_wino2.hip): every mask of RV_W2_ABL on a few BASELINE shapes (B = 8,
+fused statistics).  Results are WRONG by design for mask != 0.    python tools/w2_ablate.py
+Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation).  It reads RV_W2_ABL once, so
+every mask runs in a process of its own (this script starts them: `--mask M` is the child's form)."""
 import os
+import subprocess
 import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch
-from reconvat_amd import ops, _lib
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault('RECONVAT_HIP_LIB', os.path.join(ROOT, 'reconvat_amd', 'libreconvat_hip_abl.so'))
 
 SHAPES = [(64, 64, 160, 57), (96, 48, 160, 57), (16, 16, 640, 229), (32, 32, 320, 114), (128, 128, 80, 28)]
 MASKS = [(0, 'full'), (64, '- statistics tail'), (96, '- band epilogue'), (120, '- barrier, staging'), (122, '- patch reads / transform'),
@@ -18,6 +18,17 @@ if os.environ.get('W2_MASKS'):
     MASKS = [(int(m), '') for m in os.environ['W2_MASKS'].split(',')]
 ALGO = int(os.environ.get('W2_ALGO', '0x811'), 0)
 B = 8
+if '--mask' not in sys.argv:
+    for mask, name in [(None, 'round-4 kernel 0x611')] + MASKS:
+        env = dict(os.environ, W2_NAME=name)
+        env.pop('RV_W2_ABL', None)
+        if mask is not None:
+            env['RV_W2_ABL'] = str(mask)
+        subprocess.run([sys.executable, os.path.abspath(__file__), '--mask', str(mask)], env=env, check=True)
+    sys.exit(0)
+MASK = sys.argv[sys.argv.index('--mask') + 1]
+import torch
+from reconvat_amd import ops, _lib
 dev = torch.device('cuda:0')
 lib = _lib.load()
 st = torch.cuda.current_stream()
@@ -48,11 +59,9 @@ for cin, cout, h, w in SHAPES:
     wp = ops._pack('c3', wt, 'fwd')
     args = (0, ops.ptr(x), cin, B, h, w, cin, ops.ptr(y), cout, h, w, cout, ops.ptr(wp), ops.ptr(bias), 0)
     flops = 2.0 * B * h * w * cin * cout * 9
-    os.environ.pop('RV_W2_ABL', None)
-    told = timed(args, 0x611, stats)
-    print(f'{cin}->{cout} {h}x{w}: round-4 kernel 0x611 {told:.1f} us; MFMA-only bound at 157.3 TF: {flops / 2.25 / 157.3e6:.1f} us')
-    for mask, name in MASKS:
-        os.environ['RV_W2_ABL'] = str(mask)
+    if MASK == 'None':
+        t = timed(args, 0x611, stats)
+        print(f'{cin}->{cout} {h}x{w}: round-4 kernel 0x611 {t:.1f} us; MFMA-only bound at 157.3 TF: {flops / 2.25 / 157.3e6:.1f} us', flush=True)
+    else:
         t = timed(args, ALGO, stats)
-        print(f'    mask {mask:>3} {name:<34} {t:7.1f} us', flush=True)
-    os.environ.pop('RV_W2_ABL', None)
+        print(f'mask {MASK:>3} {os.environ.get("W2_NAME", ""):<34} {cin}->{cout} {h}x{w}: {t:7.1f} us', flush=True)

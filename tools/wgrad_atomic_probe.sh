@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # Cost probe (ablation build, wrong results by design): the row partitions of wgrad_mfma_k ADD their partial sums into ONE partial with fp32
 # atomics (RV_ABLATE=2048) instead of storing one partial each -- what an in-kernel reduction into a per-layer staging buffer would issue.
 export RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_abl.so

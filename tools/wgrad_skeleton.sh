@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # Where the non-MFMA time of wgrad_mfma_k goes (ablation build; RV_ABLATE bits: 1 no MFMAs, 2 no fragment reads, 4 stage the first row only,
 # 8 no row barriers, 16 no LDS zeroing, 32 return before the fold / partial-sum stores, 64 return at once)
 export RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_abl.so

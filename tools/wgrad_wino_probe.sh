@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # Cost probe for a Winograd F(3x3, 2x2) weight-gradient kernel, run BEFORE writing one (ablation build, wrong results by design):
 # the direct kernel wgrad_mfma_k with 4 of its 9 MFMA groups and 4 + TB of its 9 + TB fragment reads per 4-pixel k-step -- what the
 # Winograd form issues per 4 pixels (16 MFMA groups, 16 + 4 TB reads per 4 tiles = 16 pixels) --, then also with its transform adds

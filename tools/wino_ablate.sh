@@ -1,3 +1,4 @@
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # Where the Winograd kernel's time goes (timing only, ablation build): RV_ABLATE bits 1 barrier, 2 staging, 4 MFMAs, 8 epilogue,
 # 16 patch reads + input transform, 32 weight-fragment reads.
 export RECONVAT_HIP_LIB=reconvat_amd/libreconvat_hip_abl.so

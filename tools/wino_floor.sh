@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # The Winograd kernel's skeleton (ablation build, event timing; a launch-only kernel shows the host pacing floor of the loop):
 # RV_ABLATE 64 return at entry, 128 return after the staging plan, 1024 return after unit 0's DMA has landed, 63 whole loop with barrier /
 # staging / MFMAs / epilogue / transform / weight reads off, 4159 = 63 + no statistics tail.

@@ -1,4 +1,5 @@
 #!/bin/bash
+# Library: the ablation build, reconvat_amd/libreconvat_hip_abl.so (python -m reconvat_amd.build --ablation; timing only, WRONG results).
 # rocprofv3 kernel durations of the Winograd kernel's early-return probes (ablation build; see tools/wino_floor.sh for the bits)
 export RECONVAT_HIP_LIB=$GRAFT_REPO_ROOT/reconvat_amd/libreconvat_hip_abl.so
 export RV_FORCE_ALGO=${1:-0x611}
