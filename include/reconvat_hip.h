@@ -79,7 +79,12 @@ int rv_cqt_lognorm_fwd(const float* audio, long audio_stride, int B, int nsamp, 
  *   d(loss)/d(output of a BatchNorm+leaky_relu with pre-normalisation input bn_z); bn_sums then receives that layer's
  *   backward reduction (sum dd, sum dd*xhat) and rv_bn_lrelu_bwd(..., sums_ready = 1) skips its own pass over dy, z.
  * rv_conv_wgrad: G[tap][a][b] = sum_p U[f(p,tap)][a]*V[p][b] (+ column sums of V for the bias), written
- *   to dw[a*s_a + b*s_b + tap'] / dbias[b]; mode 0 = 3x3, 1 = 1x1, 2 = 2x2/s2. */
+ *   to dw[a*s_a + b*s_b + tap'] / dbias[b]; mode 0 = 3x3, 1 = 1x1, 2 = 2x2/s2.  U is [B, Hu, Wu] pixels of u_ld >= Ca floats, V
+ *   [B, Hv, Wv] pixels of v_ld >= Cb floats; modes 0 and 1 want Hu == Hv and Wu == Wv, mode 2 wants 2 Hv <= Hu <= 2 Hv + 1 and
+ *   2 Wv <= Wu <= 2 Wv + 1.  Outside the small-channel kernels (Ca * Cb * taps <= 144 with Ca < 8 or Cb < 8, and the sliced
+ *   1 -> 32 / 48 3x3 layer, which take any stride and alignment) the rows are staged by 16-byte LDS-DMA, one channel quad per lane:
+ *   Ca, Cb, u_ld and v_ld must be multiples of 4 and U and V (every segment of rv_conv_wgrad_seg) 16-byte aligned.  Anything else
+ *   is refused with -1 before a kernel is launched. */
 long rv_packed_weight_floats(int taps, int kdim, int ndim);
 int rv_pack_weights(const float* w, float* out, int taps, int kdim, int ndim, long s_k, long s_n, int flip,
                     int scatter_cmid, int force_plain, void* stream);

@@ -3298,6 +3298,10 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
     hipStream_t st = (hipStream_t)stream;
     RV_CHECK_ARG(mode >= 0 && mode <= 2, "rv_conv_wgrad: bad mode %d", mode);
     const int taps = mode == 0 ? 9 : (mode == 1 ? 1 : 4);
+    RV_CHECK_ARG(B > 0 && Hv > 0 && Wv > 0 && Ca > 0 && Cb > 0 && u_ld >= Ca && v_ld >= Cb, "rv_conv_wgrad: empty problem or a pixel stride below the channel count");
+    // f(p, tap) of every kernel indexes U with V's grid: 3x3 / 1x1 want the same grid, the 2x2/s2 gather rows 2y, 2y + 1 of 2 Hv (+ 1) rows
+    if (mode == 2) RV_CHECK_ARG(Hu >= 2 * Hv && Hu <= 2 * Hv + 1 && Wu >= 2 * Wv && Wu <= 2 * Wv + 1, "rv_conv_wgrad: mode 2 wants U of 2 Hv (+ 1) x 2 Wv (+ 1) pixels, got %d x %d for %d x %d", Hu, Wu, Hv, Wv);
+    else RV_CHECK_ARG(Hu == Hv && Wu == Wv, "rv_conv_wgrad: mode %d wants U and V on the same grid, got %d x %d and %d x %d", mode, Hu, Wu, Hv, Wv);
     if (nseg > 1 && (wgrad_sliced(taps, Ca, Cb) || B % nseg)) {
         rv_set_error("rv_conv_wgrad_seg: no segmented form for this layer (taps %d, %d -> %d channels)", taps, Ca, Cb);
         return RV_EUNSUPPORTED;
@@ -3384,6 +3388,13 @@ static int conv_wgrad_impl(int mode, const float* U, int u_ld, int Hu, int Wu, i
         rv_set_error("rv_conv_wgrad: no small-channel kernel for mode %d Ca=%d Cb=%d", mode, Ca, Cb);
         return RV_EUNSUPPORTED;
     } else {
+        // both MFMA kernels stage rows with 16-byte LDS-DMA, one channel quad per lane (`c4 < ca_valid`): a quad that straddles the end of
+        // the channel slice would be read whole -- behind the view at its last pixel -- so the channel counts are whole quads, and every
+        // quad of every pixel of every segment is 16-byte aligned
+        RV_CHECK_ARG((Ca & 3) == 0 && (Cb & 3) == 0, "rv_conv_wgrad: the MFMA kernels take channel counts that are multiples of 4 (%d -> %d)", Ca, Cb);
+        RV_CHECK_ARG((u_ld & 3) == 0 && (v_ld & 3) == 0, "rv_conv_wgrad: the MFMA kernels take pixel strides that are multiples of 4 (u_ld %d, v_ld %d)", u_ld, v_ld);
+        for (int i = 0; i < 4; ++i)
+            RV_CHECK_ARG(((((uintptr_t)a.Useg[i]) | ((uintptr_t)a.Vseg[i])) & 15) == 0, "rv_conv_wgrad: the MFMA kernels take 16-byte aligned U and V");
         const int TA = plan.TA, TB = plan.TB;
         dim3 grid(a.nparts, plan.nga * plan.ngb), blk(256);
         const int KH = mode == 0 ? 3 : (mode == 1 ? 1 : 2), SS = mode == 2 ? 2 : 1;
