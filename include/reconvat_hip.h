@@ -290,6 +290,22 @@ long rv_resample_max_coeffs(void);
 int rv_resample(const void* x, int in_dtype, long T_in, int C, long in_offset, const float* bank, int L, int M, int F, int Kp, void* y,
                 int out_dtype, long m_start, long n_out, void* stream);
 
+/* ---- additive synthesiser (reconvat_amd/synth.py has the definition): a table of partial rows rendered to audio.
+ * rows [n_rows][8] 32-bit words per row: s, e (int: first sample and end sample of the note, e > s), inc, ph (uint32: phase step per
+ * sample and start phase in units of 2^-32 turn), amp, dec (float32, dec >= 0: amplitude, decay rate per sample), A, R (int >= 1:
+ * attack and release lengths in samples).  With t = n - s, for s <= n < e + R the row contributes
+ *   amp * att * decay * rel * osc,   att = min(t + 1, A) / A,   decay = exp(-dec t),   rel = 1 for n < e, else ((e + R - n) / R)^2,
+ *   osc = sin(2 pi theta / 2^32),   theta = (ph + inc t) mod 2^32 in exact uint32 wrap-around arithmetic,
+ * and y[n] is the sum over all rows in ascending row order (one float64 accumulator per sample, float32 terms).
+ * tile_ptr [n_tiles + 1], tile_rows [tile_ptr[n_tiles]] (CSR): tile j covers the absolute samples [1024 j, 1024 (j + 1)) and lists,
+ * in ascending order, the rows whose [s, e + R) meets it; 0 <= n_tiles < 2^21.  y: n_out samples, out_dtype 0 = float32, 1 = int16
+ * (round-half-even of 32768 y, saturated); y[0] is sample n0, and [n0, n0 + n_out) must lie inside the n_tiles tiles (else -1 and
+ * nothing is written).  A tile_rows entry outside [0, n_rows) is skipped; a tile without rows writes zeros.  Every output is summed
+ * in the list's order, so its bits depend neither on n_out nor on where the calls of a long render are cut.  One launch, no
+ * atomics, allocation or synchronisation. */
+int rv_synth_render(const unsigned* rows, int n_rows, const int* tile_ptr, const int* tile_rows, int n_tiles, long n0, long n_out,
+                    void* y, int out_dtype, void* stream);
+
 /* ---- whole-song evaluation on the device: note decoding, the painted roll, the frame-metric counters.
  * Rolls are [T, 88] row-major, 1 <= T <= 2^24.  rv_eval_workspace_bytes(T): device scratch either call needs (0 for a T out of range).
  * rv_eval_decode: onsets / frames float32 (16-byte aligned, may alias), thresholds compared in float32 (x > threshold), rule 1 = rule1

@@ -7,7 +7,8 @@ train_UNet_Onset_VAT.py:28-78 / train_UNet_VAT.py:26-79) and loop semantics (:12
 (model-{ep}.pt + last-optimizer-state.pt), scalar logging of every loss key per epoch.
 MI355X-side additions: one process per GPU under torch.distributed.run (data-parallel, ONE flat RCCL
 gradient all-reduce per step), the fused FlatAdam, optional whole-step hipGraph replay (`graph=True`) and
-`train_on=Synthetic`.
+`train_on=Synthetic`, and `train_on=Rendered` / `train_on=Rendered:<folder>`: a corpus of note lists rendered to audio when the script
+starts (reconvat_amd/synth.py) -- seeded random scores, or the .tsv / .mid / .midi files of a folder.
 """
 import contextlib
 import json
@@ -70,13 +71,14 @@ def base_config(o, onset_script):
         c['validation_length'] = c['sequence_length']
     stamp = datetime.now().strftime('%y%m%d-%H%M%S')
     if 'logdir' not in o:
+        corpus = str(c['train_on']).replace(os.sep, '_')    # train_on=Rendered:<folder> names a path
         if onset_script:
             c['logdir'] = (f"{c['root']}/Unet_Onset-recons={c['reconstruction']}-XI={c['XI']}-eps={c['eps']}-alpha={c['alpha']}"
-                           f"-train_on=small_{c['small']}_{c['train_on']}-w_size={c['w_size']}-n_heads={c['n_heads']}"
+                           f"-train_on=small_{c['small']}_{corpus}-w_size={c['w_size']}-n_heads={c['n_heads']}"
                            f"-lr={c['learning_rate']}-" + stamp)
         else:
             c['logdir'] = (f"{c['root']}/Unet-recons={c['reconstruction']}-XI={c['XI']}-eps={c['eps']}-alpha={c['alpha']}"
-                           f"-train_on=small_{c['small']}_{c['train_on']}-w_size={c['w_size']}-n_heads={c['n_heads']}"
+                           f"-train_on=small_{c['small']}_{corpus}-w_size={c['w_size']}-n_heads={c['n_heads']}"
                            f"-lr={c['learning_rate']}-" + stamp)
     return c
 

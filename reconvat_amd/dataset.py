@@ -375,11 +375,92 @@ class SyntheticSegments(Dataset):
                 'velocity': torch.zeros_like(frame).to(self.device), 'label': (2 * frame + onset).to(torch.uint8)}
 
 
+class RenderedScores(PianoRollAudioDataset):
+    """Note lists rendered to audio by reconvat_amd/synth.py: a corpus with exact labels that exists wherever the
+    package runs.  Track i is in voice `voices[i % len(voices)]` with timbre seed `seed + i`; its score is `scores[i]` (tsv rows, or
+    a (name, rows) pair) or, without `scores`, `synth.random_score` of `n_samples` / 16000 seconds from RandomState([seed + i,
+    SCORE_STREAM]).  A track is {path: rendered/<voice>/<seed + i or name>, audio: int16 [n_samples], label, velocity: `paint_roll`
+    of the score}; a given score that ends after `n_samples` gets the samples it needs (its last offset and a second more: every release is shorter).
+    Nothing is cached on disk.  On a HIP `device` the audio comes from rv_synth_render, elsewhere from the float64 host path; the
+    labels do not depend on the device."""
+    SCORE_STREAM = 0x5C07E
+
+    def __init__(self, n_tracks, n_samples, voices=('struck',), seed=0, device='cpu', scores=None, sequence_length=None, crop_seed=42):
+        from . import synth
+        self.path, self.groups, self.refresh = 'rendered', [], False
+        self.sequence_length, self.device = sequence_length, device
+        self.random = np.random.RandomState(crop_seed)
+        voices = [voices] if isinstance(voices, str) else list(voices)
+        if scores is not None and len(scores) != n_tracks:
+            raise ValueError(f'{len(scores)} scores for {n_tracks} tracks')
+        self.data, self.scores = [], []
+        for i in range(int(n_tracks)):
+            timbre = synth.Timbre(voices[i % len(voices)], int(seed) + i)
+            name, length = str(timbre.seed), int(n_samples)
+            if scores is None:
+                notes = synth.random_score(np.random.RandomState([timbre.seed, self.SCORE_STREAM]), length / SAMPLE_RATE)
+            else:
+                name, notes = scores[i] if isinstance(scores[i], tuple) else (name, scores[i])
+                notes = np.asarray(notes, dtype=np.float64).reshape(-1, 4)
+                if len(notes):
+                    length = max(length, int(np.ceil(notes[:, 1].max() * SAMPLE_RATE)) + SAMPLE_RATE)
+            audio = synth.render(notes, length, timbre, device=device, out_dtype=torch.int16).cpu()
+            label, velocity = paint_roll(notes, (length - 1) // HOP_LENGTH + 1)
+            self.scores.append(notes)
+            self.data.append(dict(path=f'rendered/{timbre.voice}/{name}', audio=audio, label=torch.from_numpy(label),
+                                  velocity=torch.from_numpy(velocity)))
+
+
+def rendered_folder_scores(folder):
+    """The scores of `train_on=Rendered:<folder>`: the sorted .tsv / .mid / .midi files of the folder as (name, tsv rows); MIDI goes
+    through reconvat_amd.midi.parse_midi."""
+    files = sorted(f for f in os.listdir(folder) if f.endswith(('.tsv', '.mid', '.midi')))
+    if len(files) < 5:
+        raise ValueError(f'train_on=Rendered:{folder} needs at least five scores (.tsv, .mid or .midi: every fifth goes to test and '
+                         f'validation, the next to the labelled set, three to the unlabelled set); found {len(files)}')
+    scores = []
+    for f in files:
+        path = os.path.join(folder, f)
+        if f.endswith('.tsv'):
+            notes = np.loadtxt(path, delimiter='\t', skiprows=1, ndmin=2)
+        else:
+            from .midi import parse_midi
+            notes = parse_midi(path)
+        scores.append((f, np.asarray(notes, dtype=np.float64).reshape(-1, 4)))
+    return scores
+
+
+def _rendered_sets(sequence_length, validation_length, device, small, supersmall, folder, seed):
+    length = 2 * sequence_length + 16 * HOP_LENGTH
+    both = ('struck', 'sustained')
+    if folder is None:
+        n = 4 if supersmall else (16 if small else 64)
+        parts = {'l': (n, None), 'ul': (4 * n, None), 'test': (4, None)}
+    else:
+        scores = rendered_folder_scores(folder)
+        pick = lambda rule: [s for i, s in enumerate(scores) if rule(i % 5)]
+        parts = {'l': pick(lambda r: r == 1), 'ul': pick(lambda r: r > 1), 'test': pick(lambda r: r == 0)}
+        parts = {k: (len(v), v) for k, v in parts.items()}
+    # timbre (and, without a folder, score) seeds: labelled 1000 .., unlabelled 2000 .., test and validation 3000 ..
+    make = lambda key, voices, first, seq, **kw: RenderedScores(parts[key][0], length, voices, first, device, parts[key][1],
+                                                                  sequence_length=seq, **kw)
+    l_set = make('l', ('struck',), 1000, sequence_length, crop_seed=seed)
+    ul_set = make('ul', both, 2000, sequence_length, crop_seed=seed)
+    full = make('test', both, 3000, None)
+    val = RenderedScores(0, length, both, 3000, device, sequence_length=validation_length)
+    val.data, val.scores = full.data, full.scores             # the same held-out tracks, cropped
+    return l_set, ul_set, val, full
+
+
 def prepare_VAT_dataset(sequence_length, validation_length, refresh, device, small=False, supersmall=False,
                         dataset='MAPS', rank=0):
     """model/helper_functions.py:51-117 (same corpora per `train_on` value); 'Synthetic' is the extra option used for
-    plumbing runs and benchmarks.  `rank` offsets the crop seed so that data-parallel ranks draw different windows."""
+    plumbing runs and benchmarks, 'Rendered' / 'Rendered:<folder>' the corpus of rendered scores (every rank builds the
+    same tracks).  `rank` offsets the crop seed so that data-parallel ranks draw different windows."""
     seed = 42 + rank
+    if dataset == 'Rendered' or str(dataset).startswith('Rendered:'):
+        return _rendered_sets(sequence_length, validation_length, device, small, supersmall,
+                              dataset[len('Rendered:'):] if ':' in dataset else None, seed)
     if dataset == 'Synthetic':
         n = 4 if supersmall else (16 if small else 64)
         l_set = SyntheticSegments(n, sequence_length, seed=1 + 100 * rank, device=device)
@@ -409,4 +490,5 @@ def prepare_VAT_dataset(sequence_length, validation_length, refresh, device, sma
         val = Guqin(groups=['test'], sequence_length=validation_length, device=device, refresh=refresh)
         full = Guqin(groups=['test'], sequence_length=None, device=device, refresh=refresh)
         return l_set, ul_set, val, full
-    raise ValueError(f"train_on must be one of MAPS, Violin, String, Wind, Flute, Guqin, Synthetic (got {dataset!r})")
+    raise ValueError(f"train_on must be one of MAPS, Violin, String, Wind, Flute, Guqin, Synthetic, Rendered, Rendered:<folder> "
+                     f"(got {dataset!r})")

@@ -9,6 +9,8 @@ the validation split.  ``min_frames=`` / ``bridge_gap=`` (default 1 / 0: off) cl
 A checkpoint with an onset head (``transcriber.linear_onset.weight``) is loaded into ``UNet_Onset`` and decoded with its onset
 posteriorgram; any other checkpoint, and a run without ``weight=``, builds ``UNet``, whose frame roll serves as onset roll too.
 ``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
+``render=True`` writes ``<tag>-<name>.wav`` next to each MIDI file: the decoded notes rendered by the synthesiser (DESIGN 3.15:
+the 'struck' voice, timbre seed 0; 16 kHz, 16 bit, as long as the input) -- the transcription as something to listen to.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
 resampled to 16 kHz mono on the model's device) or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
@@ -44,8 +46,21 @@ def load_audio(path, device='cpu'):
     return torch.from_numpy(read_audio_int16(path, device)).float().div(32768.0)
 
 
+def write_rendering(path, notes, n_samples, device):
+    """The audible rendering of decoded notes (reconvat_amd/synth.py: 'struck' voice, timbre seed 0) as a 16 kHz 16-bit mono wav of
+    `n_samples` frames -- on a HIP device by rv_synth_render."""
+    from reconvat_amd import synth
+    pcm = synth.render(np.asarray(notes, dtype=np.float64).reshape(-1, 4), n_samples, synth.Timbre('struck', 0), device=device,
+                       out_dtype=torch.int16).cpu().numpy()
+    with wave.open(path, 'wb') as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(SAMPLE_RATE)
+        w.writeframes(pcm.astype('<i2').tobytes())
+
+
 def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT', min_frames=1,
-                    bridge_gap=0):
+                    bridge_gap=0, render=False):
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
         audio = load_audio(path, device).to(device)
@@ -60,10 +75,13 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
                                                      bridge_gap=bridge_gap)
         scaling = HOP_LENGTH / SAMPLE_RATE
         i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
+        keys = MIN_MIDI + np.asarray(p_est, dtype=np.float64).reshape(-1)
         p_est = np.array([midi_to_hz(MIN_MIDI + m) for m in p_est])
         midi_path = os.path.join(out_dir, tag + '-' + os.path.splitext(os.path.basename(path))[0] + '.mid')
         save_midi(midi_path, p_est, i_est, [127] * len(p_est))
         print(f'midi_path = {midi_path}  ({len(p_est)} notes)')
+        if render:                              # what the MIDI file says, to listen to: the same notes at the same velocity
+            write_rendering(midi_path[:-len('.mid')] + '.wav', np.column_stack([i_est, keys, np.full(len(keys), 127.0)]), len(audio), device)
 
 
 def load_model(weight, spec, device):
@@ -84,12 +102,12 @@ def load_model(weight, spec, device):
 
 def main(argv):
     cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel', onset_threshold=0.5,
-               frame_threshold=0.5)
+               frame_threshold=0.5, render=False)
     given = parse_cli(argv)
     cfg.update(given)
     model = load_model(cfg['weight'], cfg['spec'], cfg['device'])
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
-    cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap') if k in given}        # handed on only when given
+    cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap', 'render') if k in given}        # handed on only when given
     transcribe2midi(files, model, cfg['device'], cfg['output'], onset_threshold=cfg['onset_threshold'],
                     frame_threshold=cfg['frame_threshold'], **cleanup)
 
