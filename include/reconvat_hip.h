@@ -306,6 +306,28 @@ int rv_resample(const void* x, int in_dtype, long T_in, int C, long in_offset, c
 int rv_synth_render(const unsigned* rows, int n_rows, const int* tile_ptr, const int* tile_rows, int n_tiles, long n0, long n_out,
                     void* y, int out_dtype, void* stream);
 
+/* ---- score-to-recording alignment (reconvat_amd/align.py has the definition): banded dynamic time warping, batched.
+ * desc [P][9] int64 ON THE DEVICE, one row per pair: N (recording frames, rows), M (score frames, columns), W (band width), then the
+ * ELEMENT offsets of the pair's X [N][D] and Y [M][D] in feats, of lo [N] in lo, of cost [N][W] in cost, of dirs [N][W] in dirs and of
+ * its output in out.  Row i of a pair owns the columns lo[i] .. lo[i] + W - 1, cut off at M; lo is non-decreasing with lo[0] = 0.
+ * 1 <= W <= min(M, 8192), N + M <= 2^18.  The host does not read the table: every buffer comes with its length in elements, the
+ * kernels check each pair's row against them and against max_n / max_nm / max_w (upper bounds of N, N + M and W over the pairs, which
+ * also size the launch), and a pair that does not fit is not touched but for status -1 in its output header, if that is in range.
+ * max_w > 8192 or max_nm > 2^18 is refused with -3.
+ * rv_align_cost: cost[i][k] = rint(clip(1 - <x_i, y_(lo[i] + k)>, 0, 1) * 4095) as uint16, 0xFFFF where lo[i] + k >= M; the products
+ *   run on the f32 matrix pipe, the epilogue is float32.  1 <= D <= 4096.
+ * rv_align_dtw: D[0][0] = 2 c, D[i][j] = min(D[i-1][j-1] + 2 c, D[i-1][j] + c, D[i][j-1] + c) in uint32 over the cells of the band (a
+ *   predecessor outside it is infinite); dirs[i][k] = 0 diagonal, 1 from (i-1, j), 2 from (i, j-1), 3 unreachable or start, ties to
+ *   the lowest code (cells with lo[i] + k >= M are not written).  out: 4 + 2 N + 2 M int32 per pair: total = D[N-1][M-1] (uint32
+ *   bits), path length, status, 0, then row_lo [N], row_hi [N] (lowest / highest column of the path per row), col_lo [M], col_hi [M].
+ *   A band that does not connect the corners gives total 0xFFFFFFFF, length 0 and -1 in all four arrays.  One workgroup per pair
+ *   (anti-diagonal wavefront, three diagonals in LDS), recurrence and backtrack in one launch; all-integer, deterministic.
+ * Each is one launch, without atomics, allocation or synchronisation. */
+int rv_align_cost(const long* desc, int P, int D, int max_n, int max_w, const float* feats, long n_feats, const int* lo, long n_lo,
+                  unsigned short* cost, long n_cost, void* stream);
+int rv_align_dtw(const long* desc, int P, int max_nm, int max_w, const int* lo, long n_lo, const unsigned short* cost, long n_cost,
+                 unsigned char* dirs, long n_dirs, int* out, long n_out, void* stream);
+
 /* ---- whole-song evaluation on the device: note decoding, the painted roll, the frame-metric counters.
  * Rolls are [T, 88] row-major, 1 <= T <= 2^24.  rv_eval_workspace_bytes(T): device scratch either call needs (0 for a T out of range).
  * rv_eval_decode: onsets / frames float32 (16-byte aligned, may alias), thresholds compared in float32 (x > threshold), rule 1 = rule1

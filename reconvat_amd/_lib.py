@@ -77,6 +77,8 @@ SIGNATURES = {
     'rv_resample_max_coeffs': (L, []),
     'rv_resample': (I, [P, I, L, I, L, P, I, I, I, I, P, I, L, L, P]),
     'rv_synth_render': (I, [P, I, P, P, I, L, L, P, I, P]),
+    'rv_align_cost': (I, [P, I, I, I, I, P, L, P, L, P, L, P]),
+    'rv_align_dtw': (I, [P, I, I, I, P, L, P, L, P, L, P, L, P]),
     'rv_eval_workspace_bytes': (L, [L]),
     'rv_eval_decode': (I, [P, P, L, F, F, I, P, L, P, P, P, L, P]),
     'rv_eval_decode_clean': (I, [P, P, L, F, F, I, I, I, P, L, P, P, P, L, P]),

@@ -8,7 +8,9 @@ train_UNet_Onset_VAT.py:28-78 / train_UNet_VAT.py:26-79) and loop semantics (:12
 MI355X-side additions: one process per GPU under torch.distributed.run (data-parallel, ONE flat RCCL
 gradient all-reduce per step), the fused FlatAdam, optional whole-step hipGraph replay (`graph=True`) and
 `train_on=Synthetic`, and `train_on=Rendered` / `train_on=Rendered:<folder>`: a corpus of note lists rendered to audio when the script
-starts (reconvat_amd/synth.py) -- seeded random scores, or the .tsv / .mid / .midi files of a folder.
+starts (reconvat_amd/synth.py) -- seeded random scores, or the .tsv / .mid / .midi files of a folder; and
+`train_on=Scores:<folder>`: recordings with scores that are not aligned to them, aligned when the script starts (reconvat_amd/align.py,
+DESIGN 3.16), the recordings without a score as the unlabelled set.
 """
 import contextlib
 import json

@@ -452,12 +452,58 @@ def _rendered_sets(sequence_length, validation_length, device, small, supersmall
     return l_set, ul_set, val, full
 
 
+class ScoredRecordings(PianoRollAudioDataset):
+    """Ready-made tracks in the PianoRollAudioDataset layout (the splits of `train_on=Scores:<folder>`)."""
+
+    def __init__(self, tracks, sequence_length=None, seed=42, device='cpu'):
+        self.path, self.groups, self.refresh = 'scores', [], False
+        self.sequence_length, self.device = sequence_length, device
+        self.random = np.random.RandomState(seed)
+        self.data = list(tracks)
+        short = [t['path'] for t in self.data if sequence_length is not None and len(t['audio']) <= sequence_length]
+        if short:
+            raise ValueError(f'{short[0]}: a recording must be longer than sequence_length = {sequence_length} samples to be cropped')
+
+
+def _scored_sets(folder, sequence_length, validation_length, device, refresh, seed):
+    """`train_on=Scores:<folder>`: every name.wav with a score beside it (name.mid / .midi / .score.tsv, NOT aligned to
+    the recording) is aligned to it by reconvat_amd/align.py -- all of them in one batch, name.tsv written beside the recording; an
+    existing name.tsv is used as it is unless `refresh` -- and becomes a labelled track; every fifth of them (sorted, index % 5 == 0,
+    the rule of Rendered:<folder>) is held out for validation and test.  The recordings without a score are the unlabelled set."""
+    from . import align
+    scored, unscored = align.folder_pairs(folder)
+    if len(scored) < 5 or not unscored:
+        raise ValueError(f'train_on=Scores:{folder} needs at least five recordings name.wav with a score beside them (name.mid, name.midi or '
+                         f'name.score.tsv: every fifth is held out for validation and test) and at least one recording without a score (the '
+                         f'unlabelled set); found {len(scored)} with and {len(unscored)} without')
+    todo = [s for s in scored if refresh or not os.path.exists(os.path.join(folder, s[0] + '.tsv'))]
+    if todo:                    # (every data-parallel rank computes the same rows; write_tsv replaces the file in one step)
+        items = [(read_audio_int16(wav, device), align.read_score(score)) for _, wav, score in todo]
+        for (name, _, _), (notes, _) in zip(todo, align.align_scores(items, device=device, names=[s[0] for s in todo])):
+            align.write_tsv(os.path.join(folder, name + '.tsv'), notes)
+
+    def track(wav, tsv):
+        pcm = read_audio_int16(wav, device)
+        notes = np.loadtxt(tsv, delimiter='\t', skiprows=1, ndmin=2) if tsv else np.zeros((0, 4))
+        label, velocity = paint_roll(notes, (len(pcm) - 1) // HOP_LENGTH + 1)
+        return dict(path=wav, audio=torch.from_numpy(pcm), label=torch.from_numpy(label), velocity=torch.from_numpy(velocity))
+
+    tracks = [track(wav, os.path.join(folder, name + '.tsv')) for name, wav, _ in scored]
+    held = [t for i, t in enumerate(tracks) if i % 5 == 0]
+    l_set = ScoredRecordings([t for i, t in enumerate(tracks) if i % 5], sequence_length, seed, device)
+    ul_set = ScoredRecordings([track(wav, None) for wav in unscored], sequence_length, seed, device)
+    return l_set, ul_set, ScoredRecordings(held, validation_length, 42, device), ScoredRecordings(held, None, 42, device)
+
+
 def prepare_VAT_dataset(sequence_length, validation_length, refresh, device, small=False, supersmall=False,
                         dataset='MAPS', rank=0):
     """model/helper_functions.py:51-117 (same corpora per `train_on` value); 'Synthetic' is the extra option used for
     plumbing runs and benchmarks, 'Rendered' / 'Rendered:<folder>' the corpus of rendered scores (every rank builds the
-    same tracks).  `rank` offsets the crop seed so that data-parallel ranks draw different windows."""
+    same tracks), 'Scores:<folder>' recordings with unaligned scores, aligned on the spot.  `rank` offsets the crop seed
+    so that data-parallel ranks draw different windows."""
     seed = 42 + rank
+    if str(dataset).startswith('Scores:'):
+        return _scored_sets(dataset[len('Scores:'):], sequence_length, validation_length, device, refresh, seed)
     if dataset == 'Rendered' or str(dataset).startswith('Rendered:'):
         return _rendered_sets(sequence_length, validation_length, device, small, supersmall,
                               dataset[len('Rendered:'):] if ':' in dataset else None, seed)
@@ -490,5 +536,5 @@ def prepare_VAT_dataset(sequence_length, validation_length, refresh, device, sma
         val = Guqin(groups=['test'], sequence_length=validation_length, device=device, refresh=refresh)
         full = Guqin(groups=['test'], sequence_length=None, device=device, refresh=refresh)
         return l_set, ul_set, val, full
-    raise ValueError(f"train_on must be one of MAPS, Violin, String, Wind, Flute, Guqin, Synthetic, Rendered, Rendered:<folder> "
+    raise ValueError(f"train_on must be one of MAPS, Violin, String, Wind, Flute, Guqin, Synthetic, Rendered, Rendered:<folder>, Scores:<folder> "
                      f"(got {dataset!r})")
