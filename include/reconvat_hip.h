@@ -433,6 +433,30 @@ int rv_thick_freq_bwd(const float* dz2, const float* z2, const float* x, float* 
 int rv_thick_tconv_fwd(const float* z2, const float* wj, const float* bias, float* z3, int B, int T, int N, void* stream);
 int rv_thick_linear_dz(const float* dy, const float* wt, const float* z3, float* dz3, long M, long K, int N, void* stream);
 
+/* ---- note velocities (reconvat_amd/velocity.py has the definition) --------------------------------------------
+ * A head shared by the 88 keys: the cell (b, t, p) sees x[8 j + k] = spec[b][clamp(t - 1 + j, 0, T - 1)][table[p][k]] (0 where the
+ * table says -1), j = 0..3, k = 0..7, and x[32] = p / 88; v = sigmoid(b2 + sum_h w2[h] sigmoid(b1[h] + sum_i w1[h][i] x[i])).
+ * spec [B, T, n_bins] float32 (n_spec floats; n_bins <= 384); table [88][8] int32 ON THE HOST: every entry is checked against
+ * [-1, n_bins) before anything is launched; params: w1 [32][33], b1 [32], w2 [32], b2 = 1121 floats (n_params).  Device buffers are
+ * 4-byte aligned.
+ * rv_velocity_roll: out [B, T, 88] float32 (n_out floats), every cell.  One launch.
+ * rv_velocity_loss_grad: target, mask [B, T, 88] float32 (n_cells floats each) -> loss[0] = sum m (v - target)^2 / sum m and
+ *   grad [1121] (n_grad floats) = its gradient in params; both 0 when sum m = 0.  Only cells with m != 0 are evaluated.  Two launches:
+ *   per-workgroup partial sums in a fixed order into workspace (rv_velocity_workspace_bytes, 0 for arguments out of range), then a
+ *   float64 fold in workgroup order.  No atomics: the same bits on every run.  spec gets no gradient.
+ * rv_eval_note_velocity: onsets, velocity [T, 88] float32, notes [n][3] int32 rows (t, pitch, end) on the device as
+ *   rv_eval_decode_clean writes them -> out[i] (n_out >= n floats) = the mean of velocity[s][pitch] over t <= s < min(end, T) with
+ *   onsets[s][pitch] > onset_threshold, summed in float64 in ascending s and rounded once; 0 without such a frame.  n = 0 launches
+ *   nothing. */
+int rv_velocity_roll(const float* spec, long n_spec, int B, int T, int n_bins, const int* table, const float* params, long n_params,
+                     float* out, long n_out, void* stream);
+long rv_velocity_workspace_bytes(int B, int T);
+int rv_velocity_loss_grad(const float* spec, long n_spec, int B, int T, int n_bins, const int* table, const float* params, long n_params,
+                          const float* target, const float* mask, long n_cells, float* loss, float* grad, long n_grad, void* workspace,
+                          long workspace_bytes, void* stream);
+int rv_eval_note_velocity(const float* onsets, const float* velocity, long T, float onset_threshold, const int* notes, long n, float* out,
+                          long n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

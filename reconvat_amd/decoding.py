@@ -112,6 +112,12 @@ def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_
     them, and the only read-back is the note count followed by that many (t, pitch, end) rows.  Returns (pitches, intervals, painted):
     pitches / intervals are NumPy arrays equal to the host function's; painted is the uint8 [T, 88] roll of the notes -- what
     ``notes_to_frames`` paints -- left on the device for ``evaluate.evaluate_frames_device``."""
+    _, notes, n, painted = _decode_rows_device(onsets, frames, onset_threshold, frame_threshold, rule, min_frames, bridge_gap)
+    return _rows_to_notes(notes, n) + (painted,)
+
+
+def _decode_rows_device(onsets, frames, onset_threshold, frame_threshold, rule, min_frames, bridge_gap):
+    """rv_eval_decode_clean: (the onset roll as the kernel read it, device note rows [*, 3], their number, painted)."""
     from . import _lib
     if rule not in _RULES:
         raise NameError('Please enter the correct rule name')
@@ -134,7 +140,52 @@ def extract_notes_wo_velocity_device(onsets, frames, onset_threshold=0.5, frame_
         n = int(count.item())
     if n > max_notes:
         raise RuntimeError(f'rv_eval_decode_clean reported {n} notes, more than the bound of {max_notes}')
+    return on, notes, n, painted
+
+
+def _rows_to_notes(notes, n):
     if n == 0:
-        return np.array([]), np.array([]), painted
+        return np.array([]), np.array([])
     rows = notes[:n].cpu().numpy().astype(np.int64)
-    return rows[:, 1].copy(), np.ascontiguousarray(rows[:, [0, 2]]), painted
+    return rows[:, 1].copy(), np.ascontiguousarray(rows[:, [0, 2]])
+
+
+def note_velocities(onsets, velocity, onset_threshold, pitches, intervals):
+    """float32 [n]: per note (pitch, [t, end)) the mean of velocity[s, pitch] over t <= s < end with onsets[s, pitch] >
+    onset_threshold -- summed in float64 in ascending s, divided in float64, rounded to float32 once; 0 if no such frame exists.
+    The arithmetic of rv_eval_note_velocity (csrc/velocity.hip), bit for bit."""
+    on = (torch.as_tensor(onsets) > onset_threshold).cpu().numpy()
+    vel = torch.as_tensor(velocity).detach().to(torch.float32).cpu().numpy()
+    out = np.zeros(len(pitches), dtype=np.float32)
+    for i, (p, (a, b)) in enumerate(zip(pitches, np.asarray(intervals).reshape(-1, 2))):
+        p, a, b = int(p), int(a), min(int(b), on.shape[0])
+        v = vel[a:b, p][on[a:b, p]].astype(np.float64)
+        if v.size:
+            out[i] = np.float32(np.add.accumulate(v)[-1] / np.float64(v.size))      # accumulate: strictly left to right
+    return out
+
+
+def extract_notes_with_velocity(onsets, frames, velocity, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', min_frames=1,
+                                bridge_gap=0):
+    """``extract_notes_wo_velocity`` plus ``note_velocities`` of its notes: (pitches, intervals, velocities).  At rule2 / (1, 0) these
+    are the notes of the reference's ``extract_notes`` with its velocities (there a float32 mean)."""
+    pitches, intervals = extract_notes_wo_velocity(onsets, frames, onset_threshold, frame_threshold, rule=rule, min_frames=min_frames,
+                                                   bridge_gap=bridge_gap)
+    return pitches, intervals, note_velocities(onsets, velocity, onset_threshold, pitches, intervals)
+
+
+def extract_notes_device(onsets, frames, velocity, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', min_frames=1, bridge_gap=0):
+    """``extract_notes_with_velocity`` on the device: the notes of ``extract_notes_wo_velocity_device`` and, from the note rows while
+    they are still in HBM, rv_eval_note_velocity.  Returns (pitches, intervals, velocities float32 [n], painted)."""
+    from . import _lib
+    _lib.need_gpu(velocity)
+    on, notes, n, painted = _decode_rows_device(onsets, frames, onset_threshold, frame_threshold, rule, min_frames, bridge_gap)
+    vel = _device_roll(velocity)
+    if vel.shape != on.shape or vel.device != on.device:
+        raise ValueError(f'expected a velocity roll like the onset roll {tuple(on.shape)}, got {tuple(vel.shape)}')
+    with torch.cuda.device(on.device):
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=on.device)
+        _lib.call('rv_eval_note_velocity', on.data_ptr(), vel.data_ptr(), on.shape[0], float(onset_threshold), notes.data_ptr(), n,
+                  out.data_ptr(), out.numel(), _lib.stream())
+        velocities = out[:n].cpu().numpy()
+    return _rows_to_notes(notes, n) + (velocities, painted)

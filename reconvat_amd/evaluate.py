@@ -348,6 +348,80 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
 
 
 # ---------------------------------------------------------------------------------------------
+# note metrics with velocity (mir_eval.transcription_velocity.precision_recall_f1_overlap)
+# ---------------------------------------------------------------------------------------------
+def evaluate_notes_with_velocity(ref_intervals, ref_pitches, ref_velocities, est_intervals, est_pitches, est_velocities,
+                                 onset_tolerance=0.05, pitch_tolerance=50.0, offset_ratio=0.2, offset_min_tolerance=0.05,
+                                 velocity_tolerance=0.1, beta=1.0):
+    """(precision, recall, f-measure, average overlap ratio) over the matched pairs whose velocities agree.  The pairs come from
+    ``match_notes_sparse``; the reference velocities are mapped to (v - min) / max(1, max - min); slope and intercept of the least
+    squares line from the matched estimated velocities to the matched (mapped) reference velocities are fitted, and a pair survives
+    if |slope est + intercept - ref| < velocity_tolerance.  An empty matching, or no notes on either side, gives zeros."""
+    ref_intervals = np.asarray(ref_intervals, dtype=np.float64).reshape(-1, 2)
+    est_intervals = np.asarray(est_intervals, dtype=np.float64).reshape(-1, 2)
+    ref_v = np.asarray(ref_velocities, dtype=np.float64).reshape(-1)
+    est_v = np.asarray(est_velocities, dtype=np.float64).reshape(-1)
+    if len(ref_v) != len(ref_intervals) or len(est_v) != len(est_intervals):
+        raise ValueError('evaluate_notes_with_velocity: one velocity per note expected')
+    if len(ref_pitches) == 0 or len(est_pitches) == 0:
+        return 0.0, 0.0, 0.0, 0.0
+    m = match_notes_sparse(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance, pitch_tolerance, offset_ratio,
+                           offset_min_tolerance)
+    if not m:
+        return 0.0, 0.0, 0.0, 0.0
+    ref_v = (ref_v - ref_v.min()) / max(1.0, ref_v.max() - ref_v.min())
+    ri, ej = np.array([i for i, _ in m]), np.array([j for _, j in m])
+    design = np.stack([est_v[ej], np.ones(len(m))], axis=1)
+    slope, intercept = np.linalg.lstsq(design, ref_v[ri], rcond=None)[0]
+    keep = np.abs(slope * est_v[ej] + intercept - ref_v[ri]) < velocity_tolerance
+    m = [pair for pair, k in zip(m, keep) if k]
+    p, r = len(m) / len(est_pitches), len(m) / len(ref_pitches)
+    f = (1 + beta ** 2) * p * r / (beta ** 2 * p + r) if (p + r) > 0 else 0.0
+    ratios = []
+    for i, j in m:
+        (rs, re_), (es, ee) = ref_intervals[i], est_intervals[j]
+        ratios.append((min(re_, ee) - max(rs, es)) / (max(re_, ee) - min(rs, es)))
+    return p, r, f, float(np.mean(ratios)) if ratios else 0.0
+
+
+def evaluate_with_velocity(data, model, head, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', min_frames=1, bridge_gap=0,
+                           velocity_tolerance=0.1, **kwargs):
+    """``evaluate_wo_velocity``'s dictionary (same arguments, ``device_metrics=True``) plus ``metric/note-with-velocity/*`` and
+    ``metric/note-with-offsets-and-velocity/*`` (precision, recall, f1, overlap per song).  The estimate's velocity roll is
+    ``head`` (velocity.VelocityHead) on the spectrogram of the same audio, read per note by ``extract_notes_device``; the reference's
+    is ``label['velocity']`` read the same way.  After per-clip normalisation only the rescaled comparison made by
+    ``evaluate_notes_with_velocity`` is meaningful.  The model and the head must be on a HIP device."""
+    from .decoding import extract_notes_device
+    kwargs = dict(kwargs, device_metrics=True)
+    metrics = evaluate_wo_velocity(data, model, onset_threshold, frame_threshold, rule=rule, min_frames=min_frames, bridge_gap=bridge_gap,
+                                   **kwargs)
+    head.check_front_end(model)
+    onset, pseudo_onset = kwargs.get('onset', True), kwargs.get('pseudo_onset', False)
+    for label in data:
+        with torch.no_grad():
+            pred, _, spec = model.run_on_batch(label, None, False) if kwargs.get('VAT') else model.run_on_batch(label)
+            if spec.shape[-1] != head.centres.numel():
+                raise ValueError(f'evaluate_with_velocity: the model returned a spectrogram of shape {tuple(spec.shape)}; the head expects '
+                                 f'{head.centres.numel()} bins on the last axis')
+            roll = head(spec.reshape(1, -1, spec.shape[-1])).squeeze(0)
+        frame = pred['frame'].detach().squeeze(0).relu()
+        lab_on, lab_fr = label['onset'].squeeze(0).to(frame.device), label['frame'].squeeze(0).to(frame.device)
+        lab_vel = label['velocity'].squeeze(0).to(frame.device)
+        est_on = lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu() if onset else frame
+        p_ref, i_ref, v_ref, _ = extract_notes_device(lab_on if onset else lab_fr, lab_fr, lab_vel, rule=rule)
+        p_est, i_est, v_est, _ = extract_notes_device(est_on, frame, roll, onset_threshold, frame_threshold, rule=rule,
+                                                      min_frames=min_frames, bridge_gap=bridge_gap)
+        p_ref, i_ref = _to_eval_units(p_ref, i_ref)
+        p_est, i_est = _to_eval_units(p_est, i_est)
+        for tag, ratio in (('note-with-velocity', None), ('note-with-offsets-and-velocity', 0.2)):
+            res = evaluate_notes_with_velocity(i_ref, p_ref, 128.0 * v_ref, i_est, p_est, v_est, offset_ratio=ratio,     # MIDI units: the map divides by the range
+                                               velocity_tolerance=velocity_tolerance)
+            for k, v in zip(('precision', 'recall', 'f1', 'overlap'), res):
+                metrics[f'metric/{tag}/{k}'].append(v)
+    return metrics
+
+
+# ---------------------------------------------------------------------------------------------
 # decoding thresholds chosen on a validation set (DESIGN 3.10)
 # ---------------------------------------------------------------------------------------------
 SWEEP_KEYS = ('n_est', 'matched', 'matched_with_offsets', 'frame_tp', 'frame_est')      # int64 [n_on, n_fr] each; order of rv_eval_sweep

@@ -198,6 +198,7 @@ class CQT1992v2(nn.Module):
         Q = 1 / (2 ** (1 / bins_per_octave) - 1)
         kernels, self.kernel_width, lenghts = create_cqt_kernels(Q, sr, fmin, n_bins, bins_per_octave, norm, window, fmax)
         self.n_bins = kernels.shape[0]
+        self.fmin, self.bins_per_octave = float(fmin), int(bins_per_octave)      # the bins' centre frequencies: fmin 2^(k / bins_per_octave)
         self.register_buffer('lenghts', lenghts)
         self.register_buffer('cqt_kernels_real', torch.tensor(kernels.real).unsqueeze(1))
         self.register_buffer('cqt_kernels_imag', torch.tensor(kernels.imag).unsqueeze(1))

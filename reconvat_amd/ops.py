@@ -2068,3 +2068,77 @@ class ThickLinearFn(Function):
             gemm(z3.t(), dz, dwlt, splitk=1)
             dw = thick_wlt_grad_to_checkpoint(dwlt, ctx.channels)
         return dz3, dw, None
+
+
+# ---- note velocities (csrc/velocity.hip; the definition is reconvat_amd/velocity.py) -------------------------------------
+VELOCITY_PARAMS = 1121
+
+
+def _f32_dev(t):
+    """float32, contiguous and 4-byte aligned on its device, as the velocity kernels read their buffers."""
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _velocity_args(spec, table, params):
+    import numpy as np
+    need_gpu(spec, params)
+    if spec.dim() != 3:
+        raise ValueError(f'expected a [B, T, n_bins] spectrogram, got {tuple(spec.shape)}')
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.int32))
+    if tab.shape != (88, 8):
+        raise ValueError(f'expected an [88, 8] bin table, got {tab.shape}')
+    params = _f32_dev(params).reshape(-1)
+    if params.numel() != VELOCITY_PARAMS:
+        raise ValueError(f'expected {VELOCITY_PARAMS} packed parameters, got {params.numel()}')
+    return _f32_dev(spec), tab, params
+
+
+def velocity_roll(spec, table, params):
+    """v^ [B, T, 88] of a normalised spectrogram [B, T, n_bins] (rv_velocity_roll); `table`: velocity.harmonic_bins (host, int32
+    [88, 8]); `params`: the 1121 packed parameters."""
+    spec, tab, params = _velocity_args(spec, table, params)
+    b, t, n_bins = spec.shape
+    out = torch.empty((b, t, 88), dtype=torch.float32, device=spec.device)
+    with torch.cuda.device(spec.device):
+        call('rv_velocity_roll', ptr(spec), spec.numel(), b, t, n_bins, tab.ctypes.data, ptr(params), params.numel(), ptr(out),
+             out.numel(), stream())
+    return out
+
+
+def velocity_loss_grad(spec, table, params, target, mask):
+    """(loss [], gradient [1121]) on the device: rv_velocity_loss_grad, two launches, the same bits on every run."""
+    spec, tab, params = _velocity_args(spec, table, params)
+    need_gpu(target, mask)
+    b, t, n_bins = spec.shape
+    target, mask = _f32_dev(target), _f32_dev(mask)
+    if tuple(target.shape) != (b, t, 88) or target.shape != mask.shape:
+        raise ValueError(f'expected target and mask of shape {(b, t, 88)}, got {tuple(target.shape)} and {tuple(mask.shape)}')
+    with torch.cuda.device(spec.device):
+        ws_bytes = _lib.load().rv_velocity_workspace_bytes(b, t)
+        ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=spec.device)
+        loss = torch.empty((), dtype=torch.float32, device=spec.device)
+        grad = torch.empty(VELOCITY_PARAMS, dtype=torch.float32, device=spec.device)
+        call('rv_velocity_loss_grad', ptr(spec), spec.numel(), b, t, n_bins, tab.ctypes.data, ptr(params), params.numel(), ptr(target),
+             ptr(mask), target.numel(), ptr(loss), ptr(grad), grad.numel(), ptr(ws), ws_bytes, stream())
+    return loss, grad
+
+
+class VelocityLossFn(Function):
+    """sum m (v^ - target)^2 / sum m as a function of the packed parameters; the gradient is computed with the loss and scaled by
+    grad_output in backward.  The spectrogram gets none: the front end is fixed."""
+
+    @staticmethod
+    def forward(ctx, params, spec, table, target, mask):
+        loss, grad = velocity_loss_grad(spec, table, params, target, mask)
+        ctx.save_for_backward(grad)
+        ctx.shape = params.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        grad, = ctx.saved_tensors
+        return (grad * gout).reshape(ctx.shape), None, None, None, None
+
+
+def velocity_loss(spec, table, params, target, mask):
+    return VelocityLossFn.apply(params, spec.detach(), table, target.detach(), mask.detach())

@@ -11,6 +11,9 @@ posteriorgram; any other checkpoint, and a run without ``weight=``, builds ``UNe
 ``spec=CQT`` selects the constant-Q front end; with ``weight=`` the front end follows the checkpoint's keys.
 ``render=True`` writes ``<tag>-<name>.wav`` next to each MIDI file: the decoded notes rendered by the synthesiser (DESIGN 3.15:
 the 'struck' voice, timbre seed 0; 16 kHz, 16 bit, as long as the input) -- the transcription as something to listen to.
+``velocity=<checkpoint>`` (a ``velocity-*.pt`` of train_velocity.py) gives every note its dynamics: the velocity roll of
+the head on the spectrogram of the same audio, averaged per note on the device, as MIDI velocity clamp(rint(128 v), 1, 127) -- in the
+MIDI file and in the rendering.  Without it every note has velocity 127, as before.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
 resampled to 16 kHz mono on the model's device) or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
@@ -24,7 +27,7 @@ import torch
 
 import reconvat_amd as ra
 from reconvat_amd.constants import HOP_LENGTH, SAMPLE_RATE, MIN_MIDI
-from reconvat_amd.decoding import extract_notes_wo_velocity, extract_notes_wo_velocity_device
+from reconvat_amd.decoding import extract_notes_device, extract_notes_wo_velocity, extract_notes_wo_velocity_device
 from reconvat_amd.evaluate import midi_to_hz
 from reconvat_amd.midi import save_midi
 from reconvat_amd.sacred_lite import parse_cli
@@ -60,14 +63,22 @@ def write_rendering(path, notes, n_samples, device):
 
 
 def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT', min_frames=1,
-                    bridge_gap=0, render=False):
+                    bridge_gap=0, render=False, head=None):
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
         audio = load_audio(path, device).to(device)
         with torch.no_grad():
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
-        if frame.is_cuda:                       # decode where the posteriorgrams are (csrc/eval.hip); same notes as the host decoder
+        midi_vel = None
+        if head is not None:                    # the head's roll on the spectrogram of the same audio, read per note on the device
+            from reconvat_amd import velocity
+            with torch.no_grad():
+                roll = head(velocity.front_end(model, audio.unsqueeze(0))).squeeze(0)
+            p_est, i_est, v_est, _ = extract_notes_device(onset, frame, roll, onset_threshold, frame_threshold, rule=rule,
+                                                          min_frames=min_frames, bridge_gap=bridge_gap)
+            midi_vel = velocity.midi_velocities(v_est)
+        elif frame.is_cuda:                     # decode where the posteriorgrams are (csrc/eval.hip); same notes as the host decoder
             p_est, i_est, _ = extract_notes_wo_velocity_device(onset, frame, onset_threshold, frame_threshold, rule=rule,
                                                                min_frames=min_frames, bridge_gap=bridge_gap)
         else:
@@ -78,10 +89,11 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
         keys = MIN_MIDI + np.asarray(p_est, dtype=np.float64).reshape(-1)
         p_est = np.array([midi_to_hz(MIN_MIDI + m) for m in p_est])
         midi_path = os.path.join(out_dir, tag + '-' + os.path.splitext(os.path.basename(path))[0] + '.mid')
-        save_midi(midi_path, p_est, i_est, [127] * len(p_est))
+        save_midi(midi_path, p_est, i_est, [127] * len(p_est) if midi_vel is None else [int(v) / 127 for v in midi_vel])
         print(f'midi_path = {midi_path}  ({len(p_est)} notes)')
         if render:                              # what the MIDI file says, to listen to: the same notes at the same velocity
-            write_rendering(midi_path[:-len('.mid')] + '.wav', np.column_stack([i_est, keys, np.full(len(keys), 127.0)]), len(audio), device)
+            loud = np.full(len(keys), 127.0) if midi_vel is None else midi_vel.astype(np.float64)
+            write_rendering(midi_path[:-len('.mid')] + '.wav', np.column_stack([i_est, keys, loud]), len(audio), device)
 
 
 def load_model(weight, spec, device):
@@ -93,21 +105,33 @@ def load_model(weight, spec, device):
         spec = 'CQT' if 'spectrogram.cqt_kernels_real' in state else 'Mel'
         if 'transcriber.linear_onset.weight' in state:
             cls = ra.UNet_Onset
-    model = cls((2, 2), (2, 2), log=True, reconstruction=True, mode='imagewise', spec=spec, device=device)
+    # a checkpoint trained with reconstruction=False has no reconstructor to load
+    recon = state is None or any(k.startswith('reconstructor.') for k in state)
+    model = cls((2, 2), (2, 2), log=True, reconstruction=recon, mode='imagewise', spec=spec, device=device)
     if state is not None:
         model.load_state_dict(state)
     model.to(device).eval()
     return model
 
 
+def load_head(path, model, device):
+    """The velocity head of a checkpoint on `device`; it must have been trained on the model's front end."""
+    from reconvat_amd.velocity import VelocityHead
+    head = VelocityHead.from_state_dict(torch.load(path, map_location='cpu'))
+    head.check_front_end(model)
+    return head.to(device).eval()
+
+
 def main(argv):
     cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel', onset_threshold=0.5,
-               frame_threshold=0.5, render=False)
+               frame_threshold=0.5, render=False, velocity=None)
     given = parse_cli(argv)
     cfg.update(given)
     model = load_model(cfg['weight'], cfg['spec'], cfg['device'])
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
     cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap', 'render') if k in given}        # handed on only when given
+    if cfg['velocity']:
+        cleanup['head'] = load_head(cfg['velocity'], model, cfg['device'])
     transcribe2midi(files, model, cfg['device'], cfg['output'], onset_threshold=cfg['onset_threshold'],
                     frame_threshold=cfg['frame_threshold'], **cleanup)
 
