@@ -457,6 +457,25 @@ int rv_velocity_loss_grad(const float* spec, long n_spec, int B, int T, int n_bi
 int rv_eval_note_velocity(const float* onsets, const float* velocity, long T, float onset_threshold, const int* notes, long n, float* out,
                           long n_out, void* stream);
 
+/* ---- Viterbi note decoding: per key a three-state hidden Markov model (0 = OFF, 1 = ONSET, 2 = SUSTAIN) over the two
+ * posteriorgrams, for G parameter sets at once.  1 <= T <= 2^20, 1 <= G <= 16; rv_hmm_workspace_bytes(T, G): device scratch the call
+ * needs (0 for arguments out of range).
+ * rv_hmm_decode: onsets / frames [T, 88] float32 as for rv_eval_decode (16-byte aligned, may alias), quantised once to
+ *   q(x) = 0 unless x >= 0 (NaN, negatives), else min(255, floor(256 x)) in float32.  tables (DEVICE) [G][6][256] uint16 = EO[OFF],
+ *   EO[ONSET], EO[SUSTAIN], EF[OFF], EF[ONSET], EF[SUSTAIN]: state s costs EO[s][q(onset)] + EF[s][q(frame)] at a frame; every value
+ *   is legal.  trans (HOST) [G][12] int32 = init[3], A[3][3] row-major with A[from][to]; an entry is -1 (forbidden) or in 0..65535,
+ *   init[0] and A[0][0] must be allowed; all of it is checked before anything is launched.
+ *   alpha_0(s) = init[s] + E_0(s), alpha_t(s) = min_s' (alpha_{t-1}(s') + A[s'][s]) + E_t(s) in exact 64-bit integers; the
+ *   back-pointer of (t, s) is the LOWEST s' attaining the minimum, the last state the lowest s attaining min_s alpha_{T-1}(s).
+ *   -> states [G][T][88] uint8, the path of every key under every set, and cost [G][88] int64 (device, 8-byte aligned), that minimum.
+ *   A null pointer, T or G out of range, a trans entry out of range, a forbidden init[0] or A[0][0], or a short workspace returns
+ *   non-zero, names rv_hmm_decode in rv_last_error and launches nothing.  Parallel over time (chunks of 64 frames, the recurrence as
+ *   a product in the (min, +) semiring); six launches on `stream`, no allocation, no host synchronisation, no atomics: the same
+ *   bits on every run.  `states` holds back-pointers between the launches. */
+long rv_hmm_workspace_bytes(long T, int G);
+int rv_hmm_decode(const float* onsets, const float* frames, long T, const unsigned short* tables, const int* trans, int G,
+                  unsigned char* states, long* cost, void* workspace, long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,4 +10,5 @@ from .onset_frames import (OnsetsAndFrames_VAT_full, Frame_stack_VAT, Onset_stac
                            stepwise_VAT_frame_stack, ConvStack, Onset_Stack, Combine_Stack)
 from .thickstun import Thickstun  # noqa: F401
 from .frontend import MelSpectrogram, Normalization  # noqa: F401
+from .hmm import NoteHMM  # noqa: F401
 from .train import train_VAT_model, train_model, eval_model, FlatAdam, TrainStep, weighted_loss, cycle  # noqa: F401

@@ -90,6 +90,8 @@ SIGNATURES = {
     'rv_velocity_workspace_bytes': (L, [I, I]),
     'rv_velocity_loss_grad': (I, [P, L, I, I, I, P, P, L, P, P, L, P, P, L, P, L, P]),
     'rv_eval_note_velocity': (I, [P, P, L, F, P, L, P, L, P]),
+    'rv_hmm_workspace_bytes': (L, [L, I]),
+    'rv_hmm_decode': (I, [P, P, L, P, P, I, P, P, P, L, P]),
     'rv_lstm_flag_bytes': (L, [I]),
     'rv_lstm_fwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'rv_lstm_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),

@@ -261,8 +261,24 @@ def _frames_to_eval_units(t, freqs):
     return t.astype(np.float64) * scaling, [np.array([midi_to_hz(MIN_MIDI + midi) for midi in f]) for f in freqs]
 
 
+def _hmm_decoder(hmm, onset, device_metrics, clean):
+    """None without a model; else the decode of the estimate under ``hmm`` with the call signature of the threshold decoders (their
+    thresholds, rule and clean-up arguments are accepted and replaced by the model and ``clean``)."""
+    if hmm is None:
+        return None
+    from .hmm import NoteHMM, extract_notes_hmm, extract_notes_hmm_device
+    if not isinstance(hmm, NoteHMM):
+        raise TypeError(f'hmm must be a NoteHMM, got {type(hmm).__name__}')
+    if not onset and hmm.use_onsets:
+        raise ValueError('onset=False decodes the frame roll alone: the NoteHMM must have use_onsets=False')
+    if device_metrics:
+        return lambda on, fr, *args, **kw: extract_notes_hmm_device(on, fr, [hmm], **clean)[0]
+    return lambda on, fr, *args, **kw: extract_notes_hmm(on, fr, hmm, **clean)
+
+
 def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, save_path=None, reconstruction=True,
-                         onset=True, pseudo_onset=False, rule='rule2', VAT=False, device_metrics=False, min_frames=1, bridge_gap=0):
+                         onset=True, pseudo_onset=False, rule='rule2', VAT=False, device_metrics=False, min_frames=1, bridge_gap=0,
+                         hmm=None):
     """model/evaluate_functions.py:20-127: whole-song evaluation; returns a dict of lists with the reference's keys
     (losses, metric/note/*, metric/note-with-offsets/*, metric/frame/*, metric/MusicNet/micro_avg_P, and the *_2
     variants of the reconstruction pass).  ``save_path``: per song `<basename>.pred.mid` (the transcription, reconvat_amd/midi.py)
@@ -273,10 +289,16 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
     ``average_precision_device``; the per-frame lists of ``notes_to_frames`` are never built.  The model must be on a HIP device.
 
     ``min_frames`` / ``bridge_gap``: the note clean-up of ``extract_notes_wo_velocity``, applied to the decodes of the
-    estimate -- the ``_2`` pass included -- on either path; the labels are decoded without it."""
+    estimate -- the ``_2`` pass included -- on either path; the labels are decoded without it.
+
+    ``hmm``: a ``hmm.NoteHMM``.  Every decode of the estimate, the ``_2`` pass included, is then the Viterbi decode of that
+    model -- ``extract_notes_hmm`` or, with ``device_metrics``, ``extract_notes_hmm_device`` -- followed by the same clean-up; the labels
+    are decoded as without it, and the two threshold arguments are unused (the model carries its own).  A model that uses onsets cannot
+    decode ``onset=False``: ValueError before any song is touched."""
     from .decoding import _cleanup_args
     min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)      # a bad value raises before any song is touched
     clean = dict(min_frames=min_frames, bridge_gap=bridge_gap)
+    decode_est = _hmm_decoder(hmm, onset, device_metrics, clean)
     from sklearn.metrics import average_precision_score
     metrics = defaultdict(list)
     for label in data:
@@ -294,11 +316,12 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
             decode = extract_notes_wo_velocity
         if onset:
             p_ref, i_ref, *roll_ref = decode(lab_on, lab_fr, rule=rule)
-            p_est, i_est, *roll_est = decode(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
-                                             frame_threshold, rule=rule, **clean)
+            p_est, i_est, *roll_est = (decode_est or decode)(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
+                                                             frame_threshold, rule=rule, **clean)
         else:
             p_ref, i_ref, *roll_ref = decode(lab_fr, lab_fr, rule=rule)
-            p_est, i_est, *roll_est = decode(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule, **clean)
+            p_est, i_est, *roll_est = (decode_est or decode)(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule,
+                                                             **clean)
         if not device_metrics:
             t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
             t_est, f_est = _frames_to_eval_units(*notes_to_frames(p_est, i_est, pred['frame'].shape))
@@ -325,7 +348,7 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
         metrics['metric/frame/f1'].append(hmean([frame_metrics['Precision'] + eps, frame_metrics['Recall'] + eps]) - eps)
         metrics['metric/MusicNet/micro_avg_P'].append(average_precision(pred['frame']))
         if reconstruction and pred.get('frame2') is not None:
-            p2, i2, *roll2 = decode(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold, **clean)
+            p2, i2, *roll2 = (decode_est or decode)(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold, **clean)
             if not device_metrics:
                 t2, f2 = _frames_to_eval_units(*notes_to_frames(p2, i2, pred['frame2'].shape))
             p2, i2 = _to_eval_units(p2, i2)
@@ -633,6 +656,76 @@ def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='
             'onset_threshold': float(on_thr[a]), 'frame_threshold': float(fr_thr[b]), 'best_value': float(grids[c][criterion][a, b]),
             'songs': len(per_song[0][criterion]), 'cleanups': cleanups, 'grids': grids, 'best_cleanup': c,
             'min_frames': cleanups[c][0], 'bridge_gap': cleanups[c][1]}
+
+
+MAX_HMM_SETS = 256
+HMM_METRICS = ('note_precision', 'note_recall', 'note_f1', 'note_with_offsets_precision', 'note_with_offsets_recall',
+               'note_with_offsets_f1', 'frame_precision', 'frame_recall', 'frame_f1')
+
+
+def tune_hmm(data, model, hmms, criterion='note_f1', onset=True, pseudo_onset=False, device_metrics=True, VAT=False, min_frames=1,
+             bridge_gap=0):
+    """Choose a ``hmm.NoteHMM`` among ``hmms`` (1..256 of them; ``hmm.hmm_grid`` builds a product) on a validation set.
+    One eval-mode ``run_on_batch`` per song of ``data``, as in ``tune_thresholds``; then, with ``device_metrics`` (model on a HIP device),
+    one batched Viterbi decode per 16 sets (``extract_notes_hmm_device``), else ``extract_notes_hmm`` set by set; the metric code of
+    ``evaluate_wo_velocity`` runs per set, and the per-song values are averaged with ``np.mean``: every value equals the mean of the
+    matching ``evaluate_wo_velocity(..., hmm=h)`` list.  The labels are decoded once per song, at rule2.
+
+    Returns ``{'hmms', 'values': {metric: float64 [n]}, 'criterion', 'best_index', 'best', 'best_value', 'songs'}`` with the metrics of
+    ``HMM_METRICS``; ``best`` maximises ``values[criterion]`` (``note_f1``, ``note_with_offsets_f1`` or ``frame_f1``), ties go to the lowest
+    index."""
+    from .decoding import _cleanup_args
+    from .hmm import NoteHMM, extract_notes_hmm, extract_notes_hmm_device
+    if criterion not in SWEEP_CRITERIA:
+        raise ValueError(f'criterion must be one of {SWEEP_CRITERIA}, got {criterion!r}')
+    hmms = list(hmms)
+    if not 1 <= len(hmms) <= MAX_HMM_SETS:
+        raise ValueError(f'tune_hmm takes 1..{MAX_HMM_SETS} parameter sets, got {len(hmms)}')
+    for h in hmms:
+        if not isinstance(h, NoteHMM):
+            raise TypeError(f'hmms must hold NoteHMM objects, got {type(h).__name__}')
+        if not onset and h.use_onsets:
+            raise ValueError('onset=False decodes the frame roll alone: every NoteHMM must have use_onsets=False')
+    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
+    clean = dict(min_frames=min_frames, bridge_gap=bridge_gap)
+    matcher = match_notes_sparse if device_metrics else match_notes
+    per_song = defaultdict(list)                                        # metric -> one float64 [n] per song
+    for label in data:
+        pred, _, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
+        frame = pred['frame'].detach().squeeze(0).relu()
+        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
+        if device_metrics:
+            lab_on, lab_fr = lab_on.to(frame.device), lab_fr.to(frame.device)
+        est_on = frame if not onset else lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu()
+        ref_on = lab_on if onset else lab_fr
+        if device_metrics:
+            p_ref, i_ref, roll_ref = extract_notes_wo_velocity_device(ref_on, lab_fr, rule='rule2')
+            decoded = extract_notes_hmm_device(est_on, frame, hmms, **clean)
+        else:
+            p_ref, i_ref = extract_notes_wo_velocity(ref_on, lab_fr, rule='rule2')
+            t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
+            decoded = [extract_notes_hmm(est_on, frame, h, **clean) for h in hmms]
+        p_ref, i_ref = _to_eval_units(p_ref, i_ref)
+        song = {k: np.zeros(len(hmms), np.float64) for k in HMM_METRICS}
+        for n, (p_est, i_est, *roll_est) in enumerate(decoded):
+            if device_metrics:
+                fm = evaluate_frames_device(roll_ref, roll_est[0])
+            else:
+                fm = evaluate_frames(t_ref, f_ref, *_frames_to_eval_units(*notes_to_frames(p_est, i_est, frame.shape)))
+            p_est, i_est = _to_eval_units(p_est, i_est)
+            for name, ratio in (('note', None), ('note_with_offsets', 0.2)):
+                p, r, f, _ = evaluate_notes(i_ref, p_ref, i_est, p_est, offset_ratio=ratio, match=matcher)
+                song[name + '_precision'][n], song[name + '_recall'][n], song[name + '_f1'][n] = p, r, f
+            song['frame_precision'][n], song['frame_recall'][n] = fm['Precision'], fm['Recall']
+            song['frame_f1'][n] = hmean([fm['Precision'] + eps, fm['Recall'] + eps]) - eps
+        for k, v in song.items():
+            per_song[k].append(v)
+    if not per_song:
+        raise ValueError('tune_hmm: no song in the validation set')
+    values = {k: np.array([np.mean([s[n] for s in v]) for n in range(len(hmms))]) for k, v in per_song.items()}
+    best = int(np.argmax(values[criterion]))                            # argmax: the lowest index of equal values
+    return {'hmms': hmms, 'values': values, 'criterion': criterion, 'best_index': best, 'best': hmms[best],
+            'best_value': float(values[criterion][best]), 'songs': len(per_song[criterion])}
 
 
 def save_pianoroll(path, onsets, frames, onset_threshold=0.5, frame_threshold=0.5, zoom=4):

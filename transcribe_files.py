@@ -14,6 +14,10 @@ the 'struck' voice, timbre seed 0; 16 kHz, 16 bit, as long as the input) -- the 
 ``velocity=<checkpoint>`` (a ``velocity-*.pt`` of train_velocity.py) gives every note its dynamics: the velocity roll of
 the head on the spectrogram of the same audio, averaged per note on the device, as MIDI velocity clamp(rint(128 v), 1, 127) -- in the
 MIDI file and in the rendering.  Without it every note has velocity 127, as before.
+``decoder=hmm`` decodes the notes by Viterbi with a per-key onset / sustain / off model in place of thresholding: its
+tables come from ``onset_threshold=`` / ``frame_threshold=``, ``note_on=`` / ``note_off=`` / ``restrike=`` (default 2.0 nats each) are
+the costs of switching -- tune_hmm.py chooses all five on the validation split -- and the onset roll counts as evidence iff the
+checkpoint has an onset head.  ``min_frames=`` / ``bridge_gap=`` and ``velocity=`` work on its notes as on the threshold decoder's.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
 resampled to 16 kHz mono on the model's device) or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
@@ -63,13 +67,24 @@ def write_rendering(path, notes, n_samples, device):
 
 
 def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT', min_frames=1,
-                    bridge_gap=0, render=False, head=None):
+                    bridge_gap=0, render=False, head=None, hmm=None):
+    """``hmm``: a ``reconvat_amd.NoteHMM``.  The notes are then those of its Viterbi path (the two thresholds are unused:
+    the model carries its own), found where the posteriorgrams are; the path's ONSET roll and ONSET-or-SUSTAIN roll take the place of
+    the posteriorgrams in everything after the decode, so a note's velocity is the mean over its ONSET frames."""
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
         audio = load_audio(path, device).to(device)
         with torch.no_grad():
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
+        if hmm is not None:
+            from reconvat_amd import hmm as nh
+            if frame.is_cuda:
+                onset, frame = nh._state_rolls_device(nh.viterbi_states_device(onset, frame, [hmm])[0][0])
+            else:
+                onset, frame = (torch.from_numpy(r) for r in nh.states_to_rolls(nh.viterbi_states(onset, frame, *hmm.tables())[0]))
+            onset_threshold = frame_threshold = 0.5
+            rule = 'rule2'
         midi_vel = None
         if head is not None:                    # the head's roll on the spectrogram of the same audio, read per note on the device
             from reconvat_amd import velocity
@@ -111,6 +126,7 @@ def load_model(weight, spec, device):
     if state is not None:
         model.load_state_dict(state)
     model.to(device).eval()
+    model.has_onset_head = cls is ra.UNet_Onset         # decoder=hmm: whether the onset roll is evidence of its own
     return model
 
 
@@ -124,14 +140,19 @@ def load_head(path, model, device):
 
 def main(argv):
     cfg = dict(device='cuda:0', weight=None, input='Application/Input', output='Application/Output', spec='Mel', onset_threshold=0.5,
-               frame_threshold=0.5, render=False, velocity=None)
+               frame_threshold=0.5, render=False, velocity=None, decoder='threshold', note_on=2.0, note_off=2.0, restrike=2.0)
     given = parse_cli(argv)
     cfg.update(given)
+    if cfg['decoder'] not in ('threshold', 'hmm'):
+        raise SystemExit(f"decoder must be 'threshold' or 'hmm', got {cfg['decoder']!r}")
     model = load_model(cfg['weight'], cfg['spec'], cfg['device'])
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
     cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap', 'render') if k in given}        # handed on only when given
     if cfg['velocity']:
         cleanup['head'] = load_head(cfg['velocity'], model, cfg['device'])
+    if cfg['decoder'] == 'hmm':                 # the tables come from the two thresholds; onsets count iff the checkpoint has an onset head
+        cleanup['hmm'] = ra.NoteHMM(cfg['onset_threshold'], cfg['frame_threshold'], cfg['note_on'], cfg['note_off'], cfg['restrike'],
+                                    use_onsets=model.has_onset_head)
     transcribe2midi(files, model, cfg['device'], cfg['output'], onset_threshold=cfg['onset_threshold'],
                     frame_threshold=cfg['frame_threshold'], **cleanup)
 
