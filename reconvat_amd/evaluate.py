@@ -9,7 +9,7 @@ known answers.  ``average_precision_score`` is scikit-learn's, as in the referen
 """
 import os
 import sys
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import numpy as np
 import torch
@@ -17,8 +17,11 @@ from scipy.sparse import csr_matrix
 from scipy.sparse.csgraph import maximum_bipartite_matching
 from scipy.stats import hmean
 
+from . import _lib
 from .constants import HOP_LENGTH, SAMPLE_RATE, MIN_MIDI
-from .decoding import extract_notes_wo_velocity, extract_notes_wo_velocity_device, notes_to_frames
+from .decoding import (_RULES, NoteDecoder, _cleanup_args, _device_rolls, extract_notes_wo_velocity, extract_notes_wo_velocity_device,
+                       notes_to_frames)
+from .hmm import NoteHMM, path_notes, viterbi_states, viterbi_states_device
 from .midi import save_midi
 
 eps = sys.float_info.epsilon
@@ -57,7 +60,7 @@ def evaluate_frames(ref_time, ref_freqs, est_time, est_freqs, window=0.5):
     ref_time, est_time = np.asarray(ref_time, dtype=np.float64), np.asarray(est_time, dtype=np.float64)
     if len(ref_time) != len(est_time) or not np.allclose(ref_time, est_time):
         raise ValueError('evaluate_frames: reference and estimate must share one time base')
-    out = {}
+    counts = []
     for chroma in (False, True):
         tp = n_ref = n_est = sub = miss = fa = tot = 0
         for rf, ef in zip(ref_freqs, est_freqs):
@@ -77,15 +80,8 @@ def evaluate_frames(ref_time, ref_freqs, est_time, est_freqs, window=0.5):
             miss += max(0, nr - ne)
             fa += max(0, ne - nr)
             tot += max(nr, ne) - c
-        pre = 'Chroma ' if chroma else ''
-        out[pre + 'Precision'] = tp / n_est if n_est else 0.0
-        out[pre + 'Recall'] = tp / n_ref if n_ref else 0.0
-        out[pre + 'Accuracy'] = tp / (n_est + n_ref - tp) if (n_est + n_ref - tp) else 0.0
-        out[pre + 'Substitution Error'] = sub / n_ref if n_ref else 0.0
-        out[pre + 'Miss Error'] = miss / n_ref if n_ref else 0.0
-        out[pre + 'False Alarm Error'] = fa / n_ref if n_ref else 0.0
-        out[pre + 'Total Error'] = tot / n_ref if n_ref else 0.0
-    return out
+        counts += [tp, n_ref, n_est, sub, miss, fa, tot]
+    return _frame_metrics_from_counts(counts)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -122,7 +118,12 @@ def evaluate_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset
         return 0.0, 0.0, 0.0, 0.0
     m = (match or match_notes)(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance, pitch_tolerance, offset_ratio,
                                offset_min_tolerance)
-    p, r = len(m) / len(est_pitches), len(m) / len(ref_pitches)
+    return _scores_of_matching(m, ref_intervals, est_intervals, beta)
+
+
+def _scores_of_matching(m, ref_intervals, est_intervals, beta):
+    """(precision, recall, f-measure, average overlap ratio) of the pairs ``m`` among the (non-empty) note lists."""
+    p, r = len(m) / len(est_intervals), len(m) / len(ref_intervals)
     f = (1 + beta ** 2) * p * r / (beta ** 2 * p + r) if (p + r) > 0 else 0.0
     ratios = []
     for i, j in m:
@@ -134,9 +135,6 @@ def evaluate_notes(ref_intervals, ref_pitches, est_intervals, est_pitches, onset
 # ---------------------------------------------------------------------------------------------
 # the same metrics without the host's per-frame lists and dense note matrices
 # ---------------------------------------------------------------------------------------------
-_FRAME_KEYS = ('Precision', 'Recall', 'Accuracy', 'Substitution Error', 'Miss Error', 'False Alarm Error', 'Total Error')
-
-
 def match_notes_sparse(ref_intervals, ref_pitches, est_intervals, est_pitches, onset_tolerance=0.05, pitch_tolerance=50.0,
                        offset_ratio=0.2, offset_min_tolerance=0.05):
     """``match_notes`` without an N_ref x N_est matrix: same arguments, same pair list.
@@ -198,7 +196,6 @@ def _frame_metrics_from_counts(counts):
 def frame_counts_device(ref_roll, est_roll):
     """The fourteen integer sums behind ``evaluate_frames_device`` (rv_eval_frame_counts: plain tp, n_ref, n_est, substitutions, misses,
     false alarms, total, then the chroma seven) of two uint8 [T, 88] rolls on the device, as a list of Python ints."""
-    from . import _lib
     _lib.need_gpu(ref_roll, est_roll)
     if ref_roll.dtype != torch.uint8 or est_roll.dtype != torch.uint8:
         raise TypeError('evaluate_frames_device: uint8 rolls expected')
@@ -261,19 +258,101 @@ def _frames_to_eval_units(t, freqs):
     return t.astype(np.float64) * scaling, [np.array([midi_to_hz(MIN_MIDI + midi) for midi in f]) for f in freqs]
 
 
-def _hmm_decoder(hmm, onset, device_metrics, clean):
-    """None without a model; else the decode of the estimate under ``hmm`` with the call signature of the threshold decoders (their
-    thresholds, rule and clean-up arguments are accepted and replaced by the model and ``clean``)."""
-    if hmm is None:
-        return None
-    from .hmm import NoteHMM, extract_notes_hmm, extract_notes_hmm_device
-    if not isinstance(hmm, NoteHMM):
-        raise TypeError(f'hmm must be a NoteHMM, got {type(hmm).__name__}')
-    if not onset and hmm.use_onsets:
-        raise ValueError('onset=False decodes the frame roll alone: the NoteHMM must have use_onsets=False')
-    if device_metrics:
-        return lambda on, fr, *args, **kw: extract_notes_hmm_device(on, fr, [hmm], **clean)[0]
-    return lambda on, fr, *args, **kw: extract_notes_hmm(on, fr, hmm, **clean)
+Song = namedtuple('Song', 'label losses pred spec lab_on lab_fr ref_on est_on')
+
+
+def _songs(data, model, onset, pseudo_onset, VAT, device_metrics):
+    """The per-song pass that evaluation and tuning share: exactly one eval-mode ``run_on_batch`` per song of ``data``.  Yields a ``Song``:
+    the label, the losses, ``pred`` with its rolls relu'd and squeezed to [T, 88], the spectrogram (``run_on_batch``'s third result), the
+    label rolls -- moved to the prediction's device under ``device_metrics`` only -- and the onset rolls the reference and the estimate
+    are decoded from: the label's and the predicted onsets (``pseudo_onset``: the label's for both), or with ``onset=False`` the two
+    frame rolls.  Whatever else a metric needs of a song belongs here."""
+    for label in data:
+        pred, losses, spec = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
+        for key in ('frame', 'onset', 'frame2', 'onset2'):
+            if pred.get(key) is not None:
+                pred[key] = pred[key].detach().squeeze(0).relu()
+        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
+        if device_metrics:
+            lab_on, lab_fr = lab_on.to(pred['frame'].device), lab_fr.to(pred['frame'].device)
+        if onset:
+            yield Song(label, losses, pred, spec, lab_on, lab_fr, lab_on, lab_on if pseudo_onset else pred['onset'])
+        else:
+            yield Song(label, losses, pred, spec, lab_on, lab_fr, lab_fr, pred['frame'])
+
+
+def _eval_units(notes, shape, device_metrics):
+    """A decode (pitches, intervals, velocities, painted) of ``NoteDecoder`` in the units of the metrics: (pitches in Hz, intervals in
+    seconds, frames) -- ``frames`` the painted roll under ``device_metrics``, else the (times, pitch lists) of ``notes_to_frames``."""
+    pitches, intervals, _, painted = notes
+    frames = painted if device_metrics else _frames_to_eval_units(*notes_to_frames(pitches, intervals, shape))
+    return _to_eval_units(pitches, intervals) + (frames,)
+
+
+def _song_metrics(ref, est, device_metrics):
+    """The metrics of one estimate of one song, ``ref`` and ``est`` as ``_eval_units`` makes them: ((P, R, F, overlap) of the notes, the
+    same with offsets, the dictionary of ``evaluate_frames``, the frame F1).  ``device_metrics`` picks ``match_notes_sparse`` and
+    ``evaluate_frames_device`` over ``match_notes`` and ``evaluate_frames``: same values."""
+    (p_ref, i_ref, f_ref), (p_est, i_est, f_est) = ref, est
+    matcher = match_notes_sparse if device_metrics else match_notes
+    note = evaluate_notes(i_ref, p_ref, i_est, p_est, offset_ratio=None, match=matcher)
+    with_offsets = evaluate_notes(i_ref, p_ref, i_est, p_est, match=matcher)
+    fm = evaluate_frames_device(f_ref, f_est) if device_metrics else evaluate_frames(*f_ref, *f_est)
+    return note, with_offsets, fm, hmean([fm['Precision'] + eps, fm['Recall'] + eps]) - eps
+
+
+def _decoders(onset_threshold, frame_threshold, rule, min_frames, bridge_gap, hmm, onset):
+    """The decoders of (the labels, the estimate, the estimate of the ``_2`` pass); a bad argument raises here, before any song is touched.
+    The labels are decoded at 0.5 / 0.5 and ``rule`` without clean-up or model; the ``_2`` pass at the decoder's default rule, whatever
+    ``rule`` says, as in the reference."""
+    est = dict(min_frames=min_frames, bridge_gap=bridge_gap, hmm=hmm, onset=onset)
+    return (NoteDecoder(rule=rule), NoteDecoder(onset_threshold, frame_threshold, rule, **est),
+            NoteDecoder(onset_threshold, frame_threshold, **est))
+
+
+def _evaluate_song(metrics, song, decoders, reconstruction, device_metrics, save_path, velocities=(None, None)):
+    """``evaluate_wo_velocity`` for one ``Song``: appends its values to ``metrics`` and returns the decodes (reference, estimate) in frame
+    units.  ``velocities``: the velocity rolls the two decodes read per note, if any."""
+    from sklearn.metrics import average_precision_score
+    label, losses, pred, _, lab_on, lab_fr, ref_on, est_on = song
+    decode_ref, decode_est, decode_est2 = decoders
+    for key, loss in losses.items():
+        metrics[key].append(loss.item())
+    ref_notes = decode_ref(ref_on, lab_fr, velocities[0], device_metrics)
+    est_notes = decode_est(est_on, pred['frame'], velocities[1], device_metrics)
+    ref = _eval_units(ref_notes, lab_fr.shape, device_metrics)
+    est = _eval_units(est_notes, pred['frame'].shape, device_metrics)
+
+    def average_precision(score):
+        if device_metrics:
+            return average_precision_device(lab_fr.flatten(), score.flatten())
+        return average_precision_score(lab_fr.cpu().flatten().numpy(), score.cpu().flatten().numpy())
+
+    def block(suffix, est):
+        note, with_offsets, fm, f1 = _song_metrics(ref, est, device_metrics)
+        for tag, values in (('note', note), ('note-with-offsets', with_offsets)):
+            for k, v in zip(('precision', 'recall', 'f1', 'overlap'), values):
+                metrics[f'metric/{tag}/{k}{suffix}'].append(v)
+        metrics['metric/frame/f1' + suffix].append(f1)
+        return fm
+
+    frame_metrics = block('', est)
+    metrics['metric/MusicNet/micro_avg_P'].append(average_precision(pred['frame']))
+    if reconstruction and pred.get('frame2') is not None:
+        fm2 = block('_2', _eval_units(decode_est2(pred['onset2'], pred['frame2'], None, device_metrics), pred['frame2'].shape, device_metrics))
+        frame_metrics['Precision_2'], frame_metrics['Recall_2'], frame_metrics['accuracy_2'] = \
+            fm2['Precision'], fm2['Recall'], fm2['Accuracy']
+        metrics['metric/MusicNet/micro_avg_P2'].append(average_precision(pred['frame2']))
+    for key, value in frame_metrics.items():
+        metrics['metric/frame/' + key.lower().replace(' ', '_')].append(value)
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+        path = label['path'][0] if isinstance(label['path'], (list, tuple)) else label['path']
+        stem = os.path.join(save_path, os.path.basename(str(path)))
+        save_pianoroll(stem + '.label.png', lab_on, lab_fr)
+        save_pianoroll(stem + '.pred.png', pred['onset'] if pred.get('onset') is not None else pred['frame'], pred['frame'])
+        save_midi(stem + '.pred.mid', est[0], est[1], [127] * len(est[0]))
+    return ref_notes, est_notes
 
 
 def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, save_path=None, reconstruction=True,
@@ -284,89 +363,20 @@ def evaluate_wo_velocity(data, model, onset_threshold=0.5, frame_threshold=0.5, 
     variants of the reconstruction pass).  ``save_path``: per song `<basename>.pred.mid` (the transcription, reconvat_amd/midi.py)
     and the `<basename>.label.png` / `.pred.png` piano rolls (model/utils.py:61-80), as the reference writes them (:119-126).
 
-    ``device_metrics=True`` computes the same dictionary where the posteriorgrams are: notes and painted rolls by
-    ``extract_notes_wo_velocity_device``, frame metrics by ``evaluate_frames_device``, note matching by ``match_notes_sparse``, AP by
+    ``device_metrics=True`` computes the same dictionary where the posteriorgrams are: notes and painted rolls by the
+    device side of ``NoteDecoder``, frame metrics by ``evaluate_frames_device``, note matching by ``match_notes_sparse``, AP by
     ``average_precision_device``; the per-frame lists of ``notes_to_frames`` are never built.  The model must be on a HIP device.
 
     ``min_frames`` / ``bridge_gap``: the note clean-up of ``extract_notes_wo_velocity``, applied to the decodes of the
     estimate -- the ``_2`` pass included -- on either path; the labels are decoded without it.
 
     ``hmm``: a ``hmm.NoteHMM``.  Every decode of the estimate, the ``_2`` pass included, is then the Viterbi decode of that
-    model -- ``extract_notes_hmm`` or, with ``device_metrics``, ``extract_notes_hmm_device`` -- followed by the same clean-up; the labels
-    are decoded as without it, and the two threshold arguments are unused (the model carries its own).  A model that uses onsets cannot
-    decode ``onset=False``: ValueError before any song is touched."""
-    from .decoding import _cleanup_args
-    min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)      # a bad value raises before any song is touched
-    clean = dict(min_frames=min_frames, bridge_gap=bridge_gap)
-    decode_est = _hmm_decoder(hmm, onset, device_metrics, clean)
-    from sklearn.metrics import average_precision_score
+    model followed by the same clean-up; the labels are decoded as without it, and the two threshold arguments are unused (the model
+    carries its own).  A model that uses onsets cannot decode ``onset=False``: ValueError before any song is touched."""
+    decoders = _decoders(onset_threshold, frame_threshold, rule, min_frames, bridge_gap, hmm, onset)
     metrics = defaultdict(list)
-    for label in data:
-        pred, losses, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
-        for key, loss in losses.items():
-            metrics[key].append(loss.item())
-        for key in ('frame', 'onset', 'frame2', 'onset2'):
-            if pred.get(key) is not None:
-                pred[key] = pred[key].detach().squeeze(0).relu()
-        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
-        if device_metrics:
-            lab_on, lab_fr = lab_on.to(pred['frame'].device), lab_fr.to(pred['frame'].device)
-            decode = extract_notes_wo_velocity_device
-        else:
-            decode = extract_notes_wo_velocity
-        if onset:
-            p_ref, i_ref, *roll_ref = decode(lab_on, lab_fr, rule=rule)
-            p_est, i_est, *roll_est = (decode_est or decode)(lab_on if pseudo_onset else pred['onset'], pred['frame'], onset_threshold,
-                                                             frame_threshold, rule=rule, **clean)
-        else:
-            p_ref, i_ref, *roll_ref = decode(lab_fr, lab_fr, rule=rule)
-            p_est, i_est, *roll_est = (decode_est or decode)(pred['frame'], pred['frame'], onset_threshold, frame_threshold, rule=rule,
-                                                             **clean)
-        if not device_metrics:
-            t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
-            t_est, f_est = _frames_to_eval_units(*notes_to_frames(p_est, i_est, pred['frame'].shape))
-        p_ref, i_ref = _to_eval_units(p_ref, i_ref)
-        p_est, i_est = _to_eval_units(p_est, i_est)
-
-        matcher = match_notes_sparse if device_metrics else match_notes
-
-        def average_precision(score):
-            if device_metrics:
-                return average_precision_device(lab_fr.flatten(), score.flatten())
-            return average_precision_score(lab_fr.cpu().flatten().numpy(), score.cpu().flatten().numpy())
-
-        def note_block(suffix, pe, ie):
-            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe, offset_ratio=None, match=matcher)
-            for k, v in zip(('precision', 'recall', 'f1', 'overlap'), (p, r, f, o)):
-                metrics[f'metric/note/{k}{suffix}'].append(v)
-            p, r, f, o = evaluate_notes(i_ref, p_ref, ie, pe, match=matcher)
-            for k, v in zip(('precision', 'recall', 'f1', 'overlap'), (p, r, f, o)):
-                metrics[f'metric/note-with-offsets/{k}{suffix}'].append(v)
-
-        note_block('', p_est, i_est)
-        frame_metrics = evaluate_frames_device(roll_ref[0], roll_est[0]) if device_metrics else evaluate_frames(t_ref, f_ref, t_est, f_est)
-        metrics['metric/frame/f1'].append(hmean([frame_metrics['Precision'] + eps, frame_metrics['Recall'] + eps]) - eps)
-        metrics['metric/MusicNet/micro_avg_P'].append(average_precision(pred['frame']))
-        if reconstruction and pred.get('frame2') is not None:
-            p2, i2, *roll2 = (decode_est or decode)(pred['onset2'], pred['frame2'], onset_threshold, frame_threshold, **clean)
-            if not device_metrics:
-                t2, f2 = _frames_to_eval_units(*notes_to_frames(p2, i2, pred['frame2'].shape))
-            p2, i2 = _to_eval_units(p2, i2)
-            note_block('_2', p2, i2)
-            fm2 = evaluate_frames_device(roll_ref[0], roll2[0]) if device_metrics else evaluate_frames(t_ref, f_ref, t2, f2)
-            frame_metrics['Precision_2'], frame_metrics['Recall_2'], frame_metrics['accuracy_2'] = \
-                fm2['Precision'], fm2['Recall'], fm2['Accuracy']
-            metrics['metric/frame/f1_2'].append(hmean([fm2['Precision'] + eps, fm2['Recall'] + eps]) - eps)
-            metrics['metric/MusicNet/micro_avg_P2'].append(average_precision(pred['frame2']))
-        for key, value in frame_metrics.items():
-            metrics['metric/frame/' + key.lower().replace(' ', '_')].append(value)
-        if save_path is not None:
-            os.makedirs(save_path, exist_ok=True)
-            path = label['path'][0] if isinstance(label['path'], (list, tuple)) else label['path']
-            stem = os.path.join(save_path, os.path.basename(str(path)))
-            save_pianoroll(stem + '.label.png', lab_on, lab_fr)
-            save_pianoroll(stem + '.pred.png', pred['onset'] if pred.get('onset') is not None else pred['frame'], pred['frame'])
-            save_midi(stem + '.pred.mid', p_est, i_est, [127] * len(p_est))
+    for song in _songs(data, model, onset, pseudo_onset, VAT, device_metrics):
+        _evaluate_song(metrics, song, decoders, reconstruction, device_metrics, save_path)
     return metrics
 
 
@@ -397,47 +407,33 @@ def evaluate_notes_with_velocity(ref_intervals, ref_pitches, ref_velocities, est
     design = np.stack([est_v[ej], np.ones(len(m))], axis=1)
     slope, intercept = np.linalg.lstsq(design, ref_v[ri], rcond=None)[0]
     keep = np.abs(slope * est_v[ej] + intercept - ref_v[ri]) < velocity_tolerance
-    m = [pair for pair, k in zip(m, keep) if k]
-    p, r = len(m) / len(est_pitches), len(m) / len(ref_pitches)
-    f = (1 + beta ** 2) * p * r / (beta ** 2 * p + r) if (p + r) > 0 else 0.0
-    ratios = []
-    for i, j in m:
-        (rs, re_), (es, ee) = ref_intervals[i], est_intervals[j]
-        ratios.append((min(re_, ee) - max(rs, es)) / (max(re_, ee) - min(rs, es)))
-    return p, r, f, float(np.mean(ratios)) if ratios else 0.0
+    return _scores_of_matching([pair for pair, k in zip(m, keep) if k], ref_intervals, est_intervals, beta)
 
 
 def evaluate_with_velocity(data, model, head, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', min_frames=1, bridge_gap=0,
-                           velocity_tolerance=0.1, **kwargs):
-    """``evaluate_wo_velocity``'s dictionary (same arguments, ``device_metrics=True``) plus ``metric/note-with-velocity/*`` and
-    ``metric/note-with-offsets-and-velocity/*`` (precision, recall, f1, overlap per song).  The estimate's velocity roll is
-    ``head`` (velocity.VelocityHead) on the spectrogram of the same audio, read per note by ``extract_notes_device``; the reference's
-    is ``label['velocity']`` read the same way.  After per-clip normalisation only the rescaled comparison made by
-    ``evaluate_notes_with_velocity`` is meaningful.  The model and the head must be on a HIP device."""
-    from .decoding import extract_notes_device
-    kwargs = dict(kwargs, device_metrics=True)
-    metrics = evaluate_wo_velocity(data, model, onset_threshold, frame_threshold, rule=rule, min_frames=min_frames, bridge_gap=bridge_gap,
-                                   **kwargs)
+                           velocity_tolerance=0.1, save_path=None, reconstruction=True, onset=True, pseudo_onset=False, VAT=False, hmm=None):
+    """``evaluate_wo_velocity``'s dictionary (its arguments, always ``device_metrics=True``) plus ``metric/note-with-velocity/*`` and
+    ``metric/note-with-offsets-and-velocity/*`` (precision, recall, f1, overlap per song), in one pass: one ``run_on_batch`` per song, and
+    both halves of the dictionary describe the same note lists -- with ``hmm`` those of its Viterbi path, whose velocities are means over
+    the path's ONSET frames.  The estimate's velocity roll is ``head`` (velocity.VelocityHead) on the spectrogram of the same audio, read
+    per note by the decoder; the reference's is ``label['velocity']`` read the same way.  After per-clip normalisation only the
+    rescaled comparison made by ``evaluate_notes_with_velocity`` is meaningful.  The model and the head must be on a HIP device; a head of
+    another front end is refused before any song is touched."""
     head.check_front_end(model)
-    onset, pseudo_onset = kwargs.get('onset', True), kwargs.get('pseudo_onset', False)
-    for label in data:
+    decoders = _decoders(onset_threshold, frame_threshold, rule, min_frames, bridge_gap, hmm, onset)
+    metrics = defaultdict(list)
+    for song in _songs(data, model, onset, pseudo_onset, VAT, True):
+        spec = song.spec
+        if spec.shape[-1] != head.centres.numel():
+            raise ValueError(f'evaluate_with_velocity: the model returned a spectrogram of shape {tuple(spec.shape)}; the head expects '
+                             f'{head.centres.numel()} bins on the last axis')
         with torch.no_grad():
-            pred, _, spec = model.run_on_batch(label, None, False) if kwargs.get('VAT') else model.run_on_batch(label)
-            if spec.shape[-1] != head.centres.numel():
-                raise ValueError(f'evaluate_with_velocity: the model returned a spectrogram of shape {tuple(spec.shape)}; the head expects '
-                                 f'{head.centres.numel()} bins on the last axis')
             roll = head(spec.reshape(1, -1, spec.shape[-1])).squeeze(0)
-        frame = pred['frame'].detach().squeeze(0).relu()
-        lab_on, lab_fr = label['onset'].squeeze(0).to(frame.device), label['frame'].squeeze(0).to(frame.device)
-        lab_vel = label['velocity'].squeeze(0).to(frame.device)
-        est_on = lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu() if onset else frame
-        p_ref, i_ref, v_ref, _ = extract_notes_device(lab_on if onset else lab_fr, lab_fr, lab_vel, rule=rule)
-        p_est, i_est, v_est, _ = extract_notes_device(est_on, frame, roll, onset_threshold, frame_threshold, rule=rule,
-                                                      min_frames=min_frames, bridge_gap=bridge_gap)
-        p_ref, i_ref = _to_eval_units(p_ref, i_ref)
-        p_est, i_est = _to_eval_units(p_est, i_est)
+        lab_vel = song.label['velocity'].squeeze(0).to(roll.device)
+        ref, est = _evaluate_song(metrics, song, decoders, reconstruction, True, save_path, (lab_vel, roll))
+        (p_ref, i_ref), (p_est, i_est) = _to_eval_units(*ref[:2]), _to_eval_units(*est[:2])
         for tag, ratio in (('note-with-velocity', None), ('note-with-offsets-and-velocity', 0.2)):
-            res = evaluate_notes_with_velocity(i_ref, p_ref, 128.0 * v_ref, i_est, p_est, v_est, offset_ratio=ratio,     # MIDI units: the map divides by the range
+            res = evaluate_notes_with_velocity(i_ref, p_ref, 128.0 * ref[2], i_est, p_est, est[2], offset_ratio=ratio,     # MIDI units: the map divides by the range
                                                velocity_tolerance=velocity_tolerance)
             for k, v in zip(('precision', 'recall', 'f1', 'overlap'), res):
                 metrics[f'metric/{tag}/{k}'].append(v)
@@ -521,18 +517,12 @@ def sweep_counts_device(onset_ref, frame_ref, onset_pred, frame_pred, onset_thre
     their notes go back to the device sorted by pitch with the offset tolerance of each as a number of frames (``_offset_slack``), and
     ``rv_eval_sweep_clean`` thresholds the rolls into bit masks once per threshold and counts kept notes, matches and painted frames
     per pair.  Raises on a CPU tensor: no fallback."""
-    from . import _lib
-    from .decoding import _RULES, _cleanup_args, _device_roll
     if rule not in _RULES:
         raise NameError('Please enter the correct rule name')
     min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
     on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
-    _lib.need_gpu(onset_ref, frame_ref, onset_pred, frame_pred)
+    onset_ref, frame_ref, on, fr = _device_rolls(onset_ref, frame_ref, onset_pred, frame_pred)
     p_ref, i_ref, roll_ref = extract_notes_wo_velocity_device(onset_ref, frame_ref, rule=rule)
-    on, fr = _device_roll(onset_pred), _device_roll(frame_pred)
-    if on.dim() != 2 or on.shape != fr.shape or on.shape != roll_ref.shape or not on.device == fr.device == roll_ref.device:
-        raise ValueError(f'expected [T, 88] rolls of one song on one device, got {tuple(on.shape)}, {tuple(fr.shape)} and labels '
-                         f'{tuple(roll_ref.shape)}')
     T, dev, n_ref = on.shape[0], on.device, len(p_ref)
     rows = np.zeros((max(n_ref, 1), 5), np.int32)
     if n_ref:
@@ -614,7 +604,6 @@ def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='
     grid.  The best triple maximises ``grids[c][criterion][a, b]`` (``note_f1``, ``note_with_offsets_f1`` or ``frame_f1``).  Ties go to
     the earliest entry of ``cleanups``, then to the pair nearest (0.5, 0.5) in max-norm (distances compared after rounding to 1e-6,
     so that 0.3 and 0.7 are equally far), then to the lowest onset index, then to the lowest frame index."""
-    from .decoding import _cleanup_args
     if criterion not in SWEEP_CRITERIA:
         raise ValueError(f'criterion must be one of {SWEEP_CRITERIA}, got {criterion!r}')
     on_thr, fr_thr = _sweep_grid(onset_thresholds, frame_thresholds)
@@ -624,16 +613,8 @@ def tune_thresholds(data, model, onset_thresholds, frame_thresholds, criterion='
     cleanups = [_cleanup_args(*c) for c in cleanups]
     sweep = sweep_counts_device if device_metrics else sweep_counts_host
     per_song = [defaultdict(list) for _ in cleanups]
-    for label in data:
-        pred, _, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
-        frame = pred['frame'].detach().squeeze(0).relu()
-        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
-        if device_metrics:
-            lab_on, lab_fr = lab_on.to(frame.device), lab_fr.to(frame.device)
-        if onset:
-            rolls = (lab_on, lab_fr, lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu(), frame)
-        else:
-            rolls = (lab_fr, lab_fr, frame, frame)
+    for s in _songs(data, model, onset, pseudo_onset, VAT, device_metrics):
+        rolls = (s.ref_on, s.lab_fr, s.est_on, s.pred['frame'])
         for (min_frames, bridge_gap), lists in zip(cleanups, per_song):
             counts = sweep(*rolls, on_thr, fr_thr, rule=rule, min_frames=min_frames, bridge_gap=bridge_gap)
             song = defaultdict(lambda: np.zeros((len(on_thr), len(fr_thr)), np.float64))
@@ -667,15 +648,13 @@ def tune_hmm(data, model, hmms, criterion='note_f1', onset=True, pseudo_onset=Fa
              bridge_gap=0):
     """Choose a ``hmm.NoteHMM`` among ``hmms`` (1..256 of them; ``hmm.hmm_grid`` builds a product) on a validation set.
     One eval-mode ``run_on_batch`` per song of ``data``, as in ``tune_thresholds``; then, with ``device_metrics`` (model on a HIP device),
-    one batched Viterbi decode per 16 sets (``extract_notes_hmm_device``), else ``extract_notes_hmm`` set by set; the metric code of
-    ``evaluate_wo_velocity`` runs per set, and the per-song values are averaged with ``np.mean``: every value equals the mean of the
+    one batched Viterbi decode per 16 sets (``viterbi_states_device``), else ``viterbi_states`` set by set, and ``hmm.path_notes`` of every
+    path; the metric code of ``evaluate_wo_velocity`` runs per set, and the per-song values are averaged with ``np.mean``: every value equals the mean of the
     matching ``evaluate_wo_velocity(..., hmm=h)`` list.  The labels are decoded once per song, at rule2.
 
     Returns ``{'hmms', 'values': {metric: float64 [n]}, 'criterion', 'best_index', 'best', 'best_value', 'songs'}`` with the metrics of
     ``HMM_METRICS``; ``best`` maximises ``values[criterion]`` (``note_f1``, ``note_with_offsets_f1`` or ``frame_f1``), ties go to the lowest
     index."""
-    from .decoding import _cleanup_args
-    from .hmm import NoteHMM, extract_notes_hmm, extract_notes_hmm_device
     if criterion not in SWEEP_CRITERIA:
         raise ValueError(f'criterion must be one of {SWEEP_CRITERIA}, got {criterion!r}')
     hmms = list(hmms)
@@ -687,37 +666,22 @@ def tune_hmm(data, model, hmms, criterion='note_f1', onset=True, pseudo_onset=Fa
         if not onset and h.use_onsets:
             raise ValueError('onset=False decodes the frame roll alone: every NoteHMM must have use_onsets=False')
     min_frames, bridge_gap = _cleanup_args(min_frames, bridge_gap)
-    clean = dict(min_frames=min_frames, bridge_gap=bridge_gap)
-    matcher = match_notes_sparse if device_metrics else match_notes
+    decode_ref = NoteDecoder(rule='rule2')
     per_song = defaultdict(list)                                        # metric -> one float64 [n] per song
-    for label in data:
-        pred, _, _ = model.run_on_batch(label, None, False) if VAT else model.run_on_batch(label)
-        frame = pred['frame'].detach().squeeze(0).relu()
-        lab_on, lab_fr = label['onset'].squeeze(0), label['frame'].squeeze(0)
-        if device_metrics:
-            lab_on, lab_fr = lab_on.to(frame.device), lab_fr.to(frame.device)
-        est_on = frame if not onset else lab_on if pseudo_onset else pred['onset'].detach().squeeze(0).relu()
-        ref_on = lab_on if onset else lab_fr
-        if device_metrics:
-            p_ref, i_ref, roll_ref = extract_notes_wo_velocity_device(ref_on, lab_fr, rule='rule2')
-            decoded = extract_notes_hmm_device(est_on, frame, hmms, **clean)
+    for s in _songs(data, model, onset, pseudo_onset, VAT, device_metrics):
+        frame = s.pred['frame']
+        ref = _eval_units(decode_ref(s.ref_on, s.lab_fr, None, device_metrics), s.lab_fr.shape, device_metrics)
+        if device_metrics:                                              # all sets of the song in one batched call per 16
+            paths = viterbi_states_device(s.est_on, frame, hmms)[0]
         else:
-            p_ref, i_ref = extract_notes_wo_velocity(ref_on, lab_fr, rule='rule2')
-            t_ref, f_ref = _frames_to_eval_units(*notes_to_frames(p_ref, i_ref, lab_fr.shape))
-            decoded = [extract_notes_hmm(est_on, frame, h, **clean) for h in hmms]
-        p_ref, i_ref = _to_eval_units(p_ref, i_ref)
+            paths = [viterbi_states(s.est_on, frame, *h.tables())[0] for h in hmms]
+        decoded = [path_notes(states, None, min_frames, bridge_gap, device_metrics) for states in paths]
         song = {k: np.zeros(len(hmms), np.float64) for k in HMM_METRICS}
-        for n, (p_est, i_est, *roll_est) in enumerate(decoded):
-            if device_metrics:
-                fm = evaluate_frames_device(roll_ref, roll_est[0])
-            else:
-                fm = evaluate_frames(t_ref, f_ref, *_frames_to_eval_units(*notes_to_frames(p_est, i_est, frame.shape)))
-            p_est, i_est = _to_eval_units(p_est, i_est)
-            for name, ratio in (('note', None), ('note_with_offsets', 0.2)):
-                p, r, f, _ = evaluate_notes(i_ref, p_ref, i_est, p_est, offset_ratio=ratio, match=matcher)
+        for n, notes in enumerate(decoded):
+            note, with_offsets, fm, f1 = _song_metrics(ref, _eval_units(notes, frame.shape, device_metrics), device_metrics)
+            for name, (p, r, f, _) in (('note', note), ('note_with_offsets', with_offsets)):
                 song[name + '_precision'][n], song[name + '_recall'][n], song[name + '_f1'][n] = p, r, f
-            song['frame_precision'][n], song['frame_recall'][n] = fm['Precision'], fm['Recall']
-            song['frame_f1'][n] = hmean([fm['Precision'] + eps, fm['Recall'] + eps]) - eps
+            song['frame_precision'][n], song['frame_recall'][n], song['frame_f1'][n] = fm['Precision'], fm['Recall'], f1
         for k, v in song.items():
             per_song[k].append(v)
     if not per_song:

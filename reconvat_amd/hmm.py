@@ -15,7 +15,7 @@ import itertools
 import numpy as np
 import torch
 
-from .decoding import extract_notes_wo_velocity
+from .decoding import _device_rolls, decode_notes
 
 OFF, ONSET, SUSTAIN = 0, 1, 2
 KEYS = 88
@@ -151,13 +151,18 @@ def _as_set(h):
     return h.tables() if isinstance(h, NoteHMM) else (h[0], h[1])
 
 
+def path_notes(states, velocity=None, min_frames=1, bridge_gap=0, device=False):
+    """The notes of one Viterbi path, ``states`` [T, 88], as ``decoding.decode_notes`` returns them: what the threshold decoder finds at
+    rule2 and 0.5 / 0.5 in the path's ONSET roll and its ONSET-or-SUSTAIN roll (``device``: torch ops on the path's device, then the device
+    decoder).  A note starts where the path enters ONSET and ends at the first OFF frame; a re-strike inside a sounding note starts a
+    second note that shares its end; a note's velocity is the mean of ``velocity`` over its ONSET frames."""
+    on, fr = ((states == ONSET).to(torch.float32), (states != OFF).to(torch.float32)) if device else states_to_rolls(states)
+    return decode_notes(on, fr, velocity, 0.5, 0.5, 'rule2', min_frames, bridge_gap, device)
+
+
 def extract_notes_hmm(onsets, frames, hmm, min_frames=1, bridge_gap=0):
-    """(pitches, intervals) in frame units: the notes of the Viterbi path of ``hmm`` -- what ``extract_notes_wo_velocity`` finds at
-    rule2 and 0.5 / 0.5 in the path's ONSET roll and its ONSET-or-SUSTAIN roll.  A note starts where the path enters ONSET and ends at
-    the first OFF frame; a re-strike inside a sounding note starts a second note that shares its end."""
-    states, _ = viterbi_states(onsets, frames, *_as_set(hmm))
-    on, fr = states_to_rolls(states)
-    return extract_notes_wo_velocity(on, fr, 0.5, 0.5, rule='rule2', min_frames=min_frames, bridge_gap=bridge_gap)
+    """(pitches, intervals) in frame units: ``path_notes`` of the Viterbi path of ``hmm``."""
+    return path_notes(viterbi_states(onsets, frames, *_as_set(hmm))[0], None, min_frames, bridge_gap)[:2]
 
 
 def hmm_grid(onset_thresholds, frame_thresholds, note_on, note_off, restrike, use_onsets=True):
@@ -174,17 +179,13 @@ def viterbi_states_device(onsets, frames, hmms):
     (states uint8 [G, T, 88], cost int64 [G, 88]), both left on the device.  rv_hmm_decode takes 16 sets per call; longer lists run in
     batches of 16 on the same rolls.  Raises on CPU tensors: no fallback."""
     from . import _lib
-    from .decoding import _device_roll
-    _lib.need_gpu(onsets, frames)
     sets = []
     for h in hmms:
         tables, trans = _as_set(h)
         sets.append((_check_set(tables, trans)[0], np.asarray(trans).astype(np.int32)))       # a bad set raises here, before any launch
     if not sets:
         raise ValueError('viterbi_states_device: no parameter set')
-    on, fr = _device_roll(onsets), _device_roll(frames)
-    if on.dim() != 2 or on.shape[1] != KEYS or on.shape != fr.shape or on.device != fr.device:
-        raise ValueError(f'expected two [T, 88] rolls on one device, got {tuple(on.shape)} and {tuple(fr.shape)}')
+    on, fr = _device_rolls(onsets, frames)
     T, dev, G = on.shape[0], on.device, len(sets)
     if not 1 <= T <= MAX_DEVICE_FRAMES:
         raise ValueError(f'viterbi_states_device: T = {T} not in 1..{MAX_DEVICE_FRAMES}')
@@ -202,20 +203,9 @@ def viterbi_states_device(onsets, frames, hmms):
     return states, cost
 
 
-def _state_rolls_device(states):
-    """float32 (onset_roll, frame_roll) of one [T, 88] state roll, by torch ops on its device."""
-    return (states == ONSET).to(torch.float32), (states != OFF).to(torch.float32)
-
-
 def extract_notes_hmm_device(onsets, frames, hmms, min_frames=1, bridge_gap=0):
-    """``extract_notes_hmm`` for every set of ``hmms`` on the device: one batched Viterbi decode per 16 sets, then per set the existing
-    note decoder (rv_eval_decode_clean) on the path's two 0 / 1 rolls.  Returns one (pitches, intervals, painted) per set, as
+    """``extract_notes_hmm`` for every set of ``hmms`` on the device: one batched Viterbi decode per 16 sets, then per set ``path_notes``
+    (rv_eval_decode_clean on the path's two 0 / 1 rolls).  Returns one (pitches, intervals, painted) per set, as
     ``extract_notes_wo_velocity_device`` does."""
-    from .decoding import _decode_rows_device, _rows_to_notes
     states, _ = viterbi_states_device(onsets, frames, hmms)
-    out = []
-    for g in range(states.shape[0]):
-        on, fr = _state_rolls_device(states[g])
-        _, notes, n, painted = _decode_rows_device(on, fr, 0.5, 0.5, 'rule2', min_frames, bridge_gap)
-        out.append(_rows_to_notes(notes, n) + (painted,))
-    return out
+    return [(p, i, painted) for p, i, _, painted in (path_notes(s, None, min_frames, bridge_gap, True) for s in states)]

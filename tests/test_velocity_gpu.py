@@ -467,3 +467,47 @@ def test_evaluate_with_velocity(dev, onset_model, trained):
     # a head of another front end is refused before anything runs
     with pytest.raises(ValueError, match='front end'):
         ev.evaluate_with_velocity(songs, onset_model, V.VelocityHead('CQT', CENTRES['CQT']()).to(dev), reconstruction=False)
+
+
+class CountingModel:
+    """The model, counting its ``run_on_batch`` calls."""
+
+    def __init__(self, model):
+        self.model, self.calls = model, 0
+
+    def __getattr__(self, name):
+        return getattr(self.model, name)
+
+    def run_on_batch(self, *args, **kwargs):
+        self.calls += 1
+        return self.model.run_on_batch(*args, **kwargs)
+
+
+def test_evaluate_with_velocity_is_one_pass(dev, onset_model, trained):
+    from reconvat_amd import NoteHMM, evaluate as ev
+    from reconvat_amd.dataset import RenderedScores, crop_item
+    data = RenderedScores(2, 256 * 512, ('struck', 'sustained'), seed=70, device=dev)
+    songs = [crop_item(t, None, None, dev) for t in data.data]
+    head, counting = trained[0], CountingModel(onset_model)
+    with torch.no_grad():
+        ev.evaluate_with_velocity(songs, counting, head, reconstruction=False)
+        assert counting.calls == len(songs)                             # one forward per song for both halves of the dictionary
+    # with a model both halves describe the notes of its Viterbi path.  At the default penalties this model's posteriorgrams decode to no
+    # matching note (recall 0, printed); the second set switches for free, so that there are pairs for the velocity test to thin out
+    recalls = []
+    for h in (NoteHMM(), NoteHMM(note_on=0.0, note_off=0.0, restrike=0.0)):
+        with torch.no_grad():
+            got = ev.evaluate_with_velocity(songs, onset_model, head, reconstruction=False, hmm=h)
+            plain = ev.evaluate_wo_velocity(songs, onset_model, reconstruction=False, hmm=h, device_metrics=True)
+        for k in ('precision', 'recall', 'f1', 'overlap'):
+            assert got[f'metric/note/{k}'] == plain[f'metric/note/{k}'] and len(got[f'metric/note/{k}']) == len(songs), (h, k)
+        print(h, 'note recall:', plain['metric/note/recall'], ' with velocity:', got['metric/note-with-velocity/recall'])
+        for a, b in (('note-with-velocity', 'note'), ('note-with-offsets-and-velocity', 'note-with-offsets')):      # survivors are a subset
+            assert all(x <= y for x, y in zip(got[f'metric/{a}/recall'], got[f'metric/{b}/recall'])), (h, a)
+        recalls.append(min(plain['metric/note/recall']))
+    assert recalls[1] > 0
+    # a head of another front end is refused before the model runs at all
+    counting.calls = 0
+    with pytest.raises(ValueError, match='front end'):
+        ev.evaluate_with_velocity(songs, counting, V.VelocityHead('CQT', CENTRES['CQT']()).to(dev), reconstruction=False)
+    assert counting.calls == 0

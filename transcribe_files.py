@@ -31,7 +31,8 @@ import torch
 
 import reconvat_amd as ra
 from reconvat_amd.constants import HOP_LENGTH, SAMPLE_RATE, MIN_MIDI
-from reconvat_amd.decoding import extract_notes_device, extract_notes_wo_velocity, extract_notes_wo_velocity_device
+from reconvat_amd import velocity
+from reconvat_amd.decoding import NoteDecoder
 from reconvat_amd.evaluate import midi_to_hz
 from reconvat_amd.midi import save_midi
 from reconvat_amd.sacred_lite import parse_cli
@@ -71,34 +72,18 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
     """``hmm``: a ``reconvat_amd.NoteHMM``.  The notes are then those of its Viterbi path (the two thresholds are unused:
     the model carries its own), found where the posteriorgrams are; the path's ONSET roll and ONSET-or-SUSTAIN roll take the place of
     the posteriorgrams in everything after the decode, so a note's velocity is the mean over its ONSET frames."""
+    decode = NoteDecoder(onset_threshold, frame_threshold, rule, min_frames, bridge_gap, hmm)
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
         audio = load_audio(path, device).to(device)
         with torch.no_grad():
             pred = model.transcribe({'audio': audio.unsqueeze(0)})
+            # the head's roll on the spectrogram of the same audio, read per note by the decoder
+            roll = None if head is None else head(velocity.front_end(model, audio.unsqueeze(0))).squeeze(0)
         onset, frame = pred['onset'].squeeze(0).relu(), pred['frame'].squeeze(0).relu()
-        if hmm is not None:
-            from reconvat_amd import hmm as nh
-            if frame.is_cuda:
-                onset, frame = nh._state_rolls_device(nh.viterbi_states_device(onset, frame, [hmm])[0][0])
-            else:
-                onset, frame = (torch.from_numpy(r) for r in nh.states_to_rolls(nh.viterbi_states(onset, frame, *hmm.tables())[0]))
-            onset_threshold = frame_threshold = 0.5
-            rule = 'rule2'
-        midi_vel = None
-        if head is not None:                    # the head's roll on the spectrogram of the same audio, read per note on the device
-            from reconvat_amd import velocity
-            with torch.no_grad():
-                roll = head(velocity.front_end(model, audio.unsqueeze(0))).squeeze(0)
-            p_est, i_est, v_est, _ = extract_notes_device(onset, frame, roll, onset_threshold, frame_threshold, rule=rule,
-                                                          min_frames=min_frames, bridge_gap=bridge_gap)
-            midi_vel = velocity.midi_velocities(v_est)
-        elif frame.is_cuda:                     # decode where the posteriorgrams are (csrc/eval.hip); same notes as the host decoder
-            p_est, i_est, _ = extract_notes_wo_velocity_device(onset, frame, onset_threshold, frame_threshold, rule=rule,
-                                                               min_frames=min_frames, bridge_gap=bridge_gap)
-        else:
-            p_est, i_est = extract_notes_wo_velocity(onset, frame, onset_threshold, frame_threshold, rule=rule, min_frames=min_frames,
-                                                     bridge_gap=bridge_gap)
+        # decode where the posteriorgrams are (csrc/eval.hip, csrc/hmm.hip); same notes as the host decoder
+        p_est, i_est, v_est, _ = decode(onset, frame, roll, device=frame.is_cuda)
+        midi_vel = None if v_est is None else velocity.midi_velocities(v_est)
         scaling = HOP_LENGTH / SAMPLE_RATE
         i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
         keys = MIN_MIDI + np.asarray(p_est, dtype=np.float64).reshape(-1)
