@@ -14,6 +14,7 @@ their ``forward`` is never called -- every numeric step runs through ``reconvat_
 HIP kernels).  Activations are NHWC internally; public tensors keep the reference's shapes.
 """
 import os
+from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
@@ -22,8 +23,9 @@ import torch.nn.init as init
 from . import ops
 from .constants import N_BINS, SAMPLE_RATE, HOP_LENGTH
 from .frontend import CQT1992v2, MelSpectrogram, Normalization
-from .ops import (ARENA, BnLink, ColsumLink, GradShare, ConvFn, UpCatFn, BnActFn, LinearFn, OnsetHeadsFn, LocalAttnFn, VatPerturbFn, SLOPE, bce_mean,
+from .ops import (ARENA, BnLink, ColsumLink, GradShare, ConvFn, UpCatFn, BnActFn, LinearFn, OnsetHeadsFn, LocalAttnFn, SLOPE, bce_mean,
                   mse_mean, abs_mean)
+from .vat import VAT, zero_loss
 
 batchNorm_momentum = 0.1
 
@@ -267,85 +269,103 @@ def _l2_normalize(d, binwise=False):
     return d / torch.norm(d, dim=-1, keepdim=True)
 
 
-class UNet_VAT(nn.Module):
-    """Virtual adversarial perturbation by one power iteration (model/UNet_onset.py:101-162).
-
-    The reference back-propagates the power-iteration loss into the weights and then discards those
-    gradients with ``model.zero_grad()``; here the weights are detached for that pass, so only the
-    input-gradient chain runs (identical ``d.grad``)."""
+class UNet_VAT(VAT):
+    """model/UNet_onset.py:101-162, model/self_attention_VAT.py:147-202: BCE distance on every transcriber head; returns
+    ({'frame', 'onset'} or the frame term, r_adv, d_normalised)."""
+    nan_message = "r_adv has nan, please debug tune down the XI for VAT"
 
     def __init__(self, XI, epsilon, n_power, KL_Div, reconstruction=False):
-        super().__init__()
+        super().__init__(XI, epsilon, n_power)
         if KL_Div:
             raise NotImplementedError('KL_Div=True references undefined names in the reference '
                                       '(model/UNet_onset.py:133-134); only the BCE distance exists')
-        self.n_power = n_power
-        self.XI = XI
-        self.epsilon = epsilon
-        self.KL_Div = KL_Div
-        self.binwise = False
-        self.reconstruction = reconstruction
-        self.nan_flag = None
-        self.noise = None          # optional callable(x) -> d0 (tests inject deterministic noise)
+        self.KL_Div, self.binwise, self.reconstruction = KL_Div, False, reconstruction
 
-    @staticmethod
-    def _outputs(model, x, detach=False):
+    def outputs(self, model, x, detach=False):
         out = model.transcriber(x, detach) if detach else model.transcriber(x)
         return out[:-1]            # (frame[, onset]) without the attention map
 
-    def power_iteration(self, model, x, refs=None):
-        """Everything of the VAT call that needs no weight gradients: the target predictions (`refs`: the
-        transcriber's outputs on `x` if the caller already has them -- run_on_batch reuses its main forward pass,
-        see _Base._vat_reusing_forward), the power iteration (forward on x + XI*d, input-gradient backward) and the
-        adversarial input.  Returns (x_adv, r_adv, d_normalised, refs)."""
-        if self.nan_flag is None or self.nan_flag.device != x.device:
-            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        if refs is None:
-            with torch.no_grad():
-                refs = self._outputs(model, x)
+    def terms(self, preds, refs):
+        return [bce_mean(p, r) for p, r in zip(preds, refs)]
+
+    def package(self, terms):
+        return {'frame': terms[0], 'onset': terms[1]} if len(terms) == 2 else terms[0]
+
+
+@dataclass
+class StepPlan:
+    """What _Base._step_plan ran before the loss table: the labelled spectrogram, the main transcriber pass if it has run
+    already (`first`), the VAT terms of both groups (zero_loss() where a branch did not run) and, from the two-stream
+    schedule, the reconstruction branch's (outputs, losses) launched on the side stream (`pack`)."""
+    spec: torch.Tensor = None
+    first: tuple = None
+    lds_ul: object = None
+    r_norm_ul: torch.Tensor = None
+    lds_l: object = None
+    r_adv: torch.Tensor = None
+    r_norm_l: torch.Tensor = None
+    pack: tuple = None
+
+
+def _hand_off(stream, *tensors):
+    """Tensors produced on another stream are consumed on `stream` from now on."""
+    for t in tensors:
+        t.record_stream(stream)
+
+
+def vat_terms(losses, training, plan):
+    """Append the VAT keys every run_on_batch ends with: LDS_l[_head], LDS_ul[_head] (training), r_norm_l, r_norm_ul (training)."""
+    tag = 'train' if training else 'test'
+    for group, lds in (('l', plan.lds_l), ('ul', plan.lds_ul)) if training else (('l', plan.lds_l),):
+        if isinstance(lds, dict):
+            for h, v in lds.items():
+                losses[f'loss/{tag}_LDS_{group}_{h}'] = v
         else:
-            refs = tuple(r.detach() for r in refs)
-        d = (self.noise(x) if self.noise is not None else torch.randn_like(x)).requires_grad_(True)
-        g = None
-        for it in range(self.n_power):
-            if it > 0:
-                d = (g * 1e10).requires_grad_(True)
-            x_adv = VatPerturbFn.apply(x, d, float(self.XI))
-            preds = self._outputs(model, x_adv, detach=True)
-            loss = None
-            for p, r in zip(preds, refs):
-                term = bce_mean(p, r)
-                loss = term if loss is None else loss + term
-            g, = torch.autograd.grad(loss, d)
-            g = g.detach()
-        # d = d.grad * 1e10 ; r_adv = eps * d / ||d||   (model/UNet_onset.py:141-151).  n_power = 0: the loop body never runs in the
-        # reference either, d stays the random draw and r_adv = eps * d / ||d|| (a RANDOM, not adversarial, perturbation)
-        if g is None:
-            x_adv, r_adv, d_norm = ops.vat_adversarial(x, d.detach(), 1.0, float(self.epsilon), self.nan_flag)
-        else:
-            x_adv, r_adv, d_norm = ops.vat_adversarial(x, g, 1e10, float(self.epsilon), self.nan_flag)
-        return x_adv, r_adv, d_norm, refs
+            losses[f'loss/{tag}_LDS_{group}'] = lds
+    losses[f'loss/{tag}_r_norm_l'] = plan.r_norm_l
+    if training:
+        losses['loss/train_r_norm_ul'] = plan.r_norm_ul
+    return losses
 
-    def check_nan(self):
-        if not torch.cuda.is_current_stream_capturing():
-            assert int(self.nan_flag.item()) == 0, \
-                "r_adv has nan, please debug tune down the XI for VAT"
 
-    def final_loss(self, model, x_adv, refs):
-        """The grad-enabled pass on the adversarial input and its distance to the target predictions."""
-        preds = self._outputs(model, x_adv)
-        losses = [bce_mean(p, r) for p, r in zip(preds, refs)]
-        if len(losses) == 2:
-            return {'frame': losses[0], 'onset': losses[1]}
-        return losses[0]
-
-    def forward(self, model, x, refs=None):
-        x_adv, r_adv, d_norm, refs = self.power_iteration(model, x, refs)
-        self.check_nan()
-        return self.final_loss(model, x_adv, refs), r_adv, d_norm
+def step_tables(heads, training, labels, plan, out, ul=None):
+    """The `predictions` and `losses` of the U-Net models' run_on_batch, from the step plan, the class's `heads` and the
+    forward outputs `out` ({'frame'[, 'onset'], 'attention'} and, with the reconstructor, {'reconstruction', 'frame2'[,
+    'onset2']}).  Losses of `plan.pack` were launched on the side stream already; the others are launched here, in key order.
+    The frame-only model answers 'onset' / 'onset2' with its frame heads.  `ul`: (ul_frame, ul_frame2) of
+    run_on_batch_application, whose training step adds them and their consistency term."""
+    tag = 'train' if training else 'test'
+    recon = 'reconstruction' in out
+    side = plan.pack[1] if plan.pack is not None else {}
+    val = dict(out, r_adv=plan.r_adv)
+    if not training:
+        for k in ('frame', 'frame2') if recon else ('frame',):
+            val[k] = val[k].reshape(*labels['frame'].shape)
+    val.setdefault('onset', val['frame'])
+    if recon:
+        val.setdefault('onset2', val['frame2'])
+        order = (heads if len(heads) == 2 else ('onset', 'frame')) + ('frame2', 'onset2')
+        if ul is not None and training:
+            val['ul_frame'], val['ul_frame2'] = ul
+            order += ('ul_frame', 'ul_frame2')
+        order += ('attention', 'r_adv', 'reconstruction')
+    else:
+        order = ('onset', 'frame', 'r_adv', 'attention')
+    predictions = {k: val[k] for k in order}
+    losses = {}
+    if recon:
+        losses[f'loss/{tag}_reconstruction'] = side['reconstruction'] if side else mse_mean(val['reconstruction'].squeeze(1), plan.spec.squeeze(1))
+    for k in [h + s for h in heads for s in (('', '2') if recon else ('',))]:
+        losses[f'loss/{tag}_{k}'] = side[k] if k in side else bce_mean(val[k], labels[k.rstrip('2')])
+    if ul is not None and training:
+        losses['loss/ul_consistency_wrt1'] = bce_mean(ul[1], ul[0].detach())
+    return predictions, vat_terms(losses, training, plan)
 
 
 class _Base(nn.Module):
+    heads = ()                           # the transcriber's posteriorgrams, in output order (the U-Net models set it)
+    recon_on_side_stream = False         # two-stream step: reconstruction branch on the side stream, beside the VAT final passes
+
     def __init__(self, log, reconstruction, mode, spec, XI, eps):
         super().__init__()
         # spec='CQT' (the reference's constructor default, model/UNet_onset.py:342-352): 88 * 2 constant-Q bins from 27.5 Hz at
@@ -414,7 +434,8 @@ class _Base(nn.Module):
           gradients go to the side stream's twin of the flat gradient bucket (ops.SIDE_GRADS, folded in by TrainStep);
         * every BatchNorm running-statistic update of the concurrent passes is deferred and replayed on this stream in
           the reference's order: UL target, UL xi*d, UL final, L target, L xi*d, L final, main forward, R, T(recon).
-        `recon_fn(first, spec)` runs the reconstruction branch (None: model without reconstructor).
+        `recon_fn(first, spec)` runs the reconstruction branch and returns its (outputs, losses) dictionaries (None: no
+        reconstructor, or a model that keeps the branch on this stream -- `recon_on_side_stream`).
         Returns (spec_l, main outputs, lds_ul, d_ul, lds_l, r_adv_l, d_l, recon_fn's result)."""
         cur = torch.cuda.current_stream()
         side = ops.side_stream(audio_l.device)
@@ -435,29 +456,88 @@ class _Base(nn.Module):
             main_done.record(cur)
             with torch.cuda.stream(side):
                 side.wait_event(main_done)
-                for t in (spec,) + tuple(out):
-                    t.record_stream(side)
+                _hand_off(side, spec, *out)
                 with ops.deferred_bn_updates() as pend_r:
                     pack = recon_fn(out, spec)
         with ops.deferred_bn_updates() as pend_l:
             xa_l, r_l, dn_l, refs_l = self.vat_loss.power_iteration(self, spec, refs=out[:-1])
         cur.wait_event(ul_done)
-        for t in (spec_ul, xa_ul, r_ul, dn_ul) + tuple(refs_ul):
-            t.record_stream(cur)                              # produced on the side stream, consumed here from now on
+        _hand_off(cur, spec_ul, xa_ul, r_ul, dn_ul, *refs_ul)
         with ops.deferred_bn_updates() as pend_ulf:
             lds_ul = self.vat_loss.final_loss(self, xa_ul, refs_ul)
         with ops.deferred_bn_updates() as pend_lf:
             lds_l = self.vat_loss.final_loss(self, xa_l, refs_l)
         cur.wait_stream(side)
         if pack is not None:
-            for t in pack.values():
-                t.record_stream(cur)
+            _hand_off(cur, *pack[0].values(), *pack[1].values())
         # every running-statistic update of the step, in the reference's order, in ONE launch (pend_main twice: the
         # labelled no_grad target pass and the main forward pass are the same computation)
         seq = [pend_ul, pend_ulf, pend_main, pend_l, pend_lf, pend_main] + ([pend_r] if pend_r is not None else [])
         ops.replay_bn_updates(seq, audio_l.device)
         self.vat_loss.check_nan()
         return spec, out, lds_ul, dn_ul, lds_l, r_l, dn_l, pack
+
+    def _branches(self, spec, first=None):
+        """forward()'s tuple by name: the transcriber's heads and attention map (`first` if that pass has run already) and, with
+        the reconstructor, 'reconstruction' and the heads of the second transcriber pass as 'frame2'[, 'onset2']."""
+        out = self(spec, first)
+        named = {}
+        if self.reconstruction:
+            named['reconstruction'], out = out[0], out[1:]
+        named.update(zip([h + s for s in ('', '2') for h in self.heads], out[:-1]))
+        named['attention'] = out[-1]
+        return named
+
+    def _recon_side(self, first, spec, labels):
+        """The reconstruction branch and its three losses, for the side stream of _vat_two_streams: (outputs, losses)."""
+        out = self._branches(spec, first)
+        new = {k: out[k] for k in ('reconstruction',) + tuple(h + '2' for h in self.heads)}
+        losses = {'reconstruction': mse_mean(new['reconstruction'].squeeze(1), spec.squeeze(1))}
+        for h in self.heads:
+            losses[h + '2'] = bce_mean(new[h + '2'], labels[h])
+        return new, losses
+
+    def _no_vat(self):
+        """(LDS, r_norm) of a group whose VAT branch does not run, in the shape vat_loss returns them."""
+        return ({h: zero_loss() for h in self.heads} if len(self.heads) == 2 else zero_loss()), zero_loss()
+
+    def _labelled_plan(self, plan, audio_l, VAT):
+        """The labelled half of the step: front-end, then VAT with forward reuse (which leaves the main pass in `first`) or none."""
+        plan.spec = self._front(audio_l, audio_l.shape[-1])
+        if VAT:
+            plan.first, plan.lds_l, r_adv, r_norm_l = self._vat_reusing_forward(plan.spec)
+            plan.r_adv = r_adv.squeeze(1)
+            plan.r_norm_l = abs_mean(r_norm_l)
+        else:
+            plan.lds_l, plan.r_norm_l = self._no_vat()
+        return plan
+
+    def _step_plan(self, audio_l, batch_ul, VAT, labels):
+        """What runs where before the loss table: both groups on two streams (_vat_two_streams), or the unlabelled VAT (if
+        there is an unlabelled batch) followed by the labelled half.  The unlabelled noise is drawn before the labelled."""
+        plan = StepPlan()
+        if bool(batch_ul) and VAT and self.training and ops.DUAL_STREAM[0] and audio_l.is_cuda:
+            recon_fn = (lambda first, spec: self._recon_side(first, spec, labels)) if self.reconstruction and self.recon_on_side_stream else None
+            plan.spec, plan.first, plan.lds_ul, r_norm_ul, plan.lds_l, r_adv, r_norm_l, plan.pack = self._vat_two_streams(
+                batch_ul['audio'], audio_l, recon_fn)
+            plan.r_norm_ul, plan.r_norm_l, plan.r_adv = abs_mean(r_norm_ul), abs_mean(r_norm_l), r_adv.squeeze(1)
+            return plan
+        if batch_ul:
+            plan.lds_ul, _, r_norm_ul = self.vat_loss(self, self._front(batch_ul['audio'], audio_l.shape[-1]))
+            plan.r_norm_ul = abs_mean(r_norm_ul)
+        else:
+            plan.lds_ul, plan.r_norm_ul = self._no_vat()
+        return self._labelled_plan(plan, audio_l, VAT)
+
+    def run_on_batch(self, batch, batch_ul=None, VAT=False):
+        labels = {h: batch[h].unsqueeze(0) if batch[h].dim() == 2 else batch[h] for h in self.heads}
+        plan = self._step_plan(batch['audio'], batch_ul, VAT, labels)
+        if plan.pack is not None:
+            out = dict(zip(self.heads + ('attention',), plan.first), **plan.pack[0])
+        else:
+            out = self._branches(plan.spec, plan.first)
+        predictions, losses = step_tables(self.heads, self.training, labels, plan, out)
+        return predictions, losses, plan.spec.squeeze(1)
 
     def load_my_state_dict(self, state_dict):
         own_state = self.state_dict()
@@ -475,6 +555,9 @@ class _Base(nn.Module):
 
 
 class UNet_Onset(_Base):
+    heads = ('frame', 'onset')
+    recon_on_side_stream = True
+
     def __init__(self, ds_ksize, ds_stride, log=True, reconstruction=True, mode='imagewise', spec='CQT', device='cpu',
                  XI=1e-6, eps=1e-2):
         super().__init__(log, reconstruction, mode, spec, XI, eps)
@@ -490,88 +573,6 @@ class UNet_Onset(_Base):
             return reconstruction, pianoroll, onset, pianoroll2, onset2, a
         return pianoroll, onset, a
 
-    def run_on_batch(self, batch, batch_ul=None, VAT=False):
-        audio_label = batch['audio']
-        onset_label = batch['onset']
-        frame_label = batch['frame']
-        if frame_label.dim() == 2:
-            frame_label = frame_label.unsqueeze(0)
-        if onset_label.dim() == 2:
-            onset_label = onset_label.unsqueeze(0)
-        dual = bool(batch_ul) and VAT and self.training and ops.DUAL_STREAM[0] and audio_label.is_cuda
-        pack = None
-        if dual:
-            def recon_fn(first_, spec_):
-                rec_, _, _, roll2_, onset2_, _ = self(spec_, first_)
-                return {'rec': rec_, 'frame2': roll2_, 'onset2': onset2_,
-                        'l_rec': mse_mean(rec_.squeeze(1), spec_.squeeze(1)),
-                        'l_frame2': bce_mean(roll2_, frame_label), 'l_onset2': bce_mean(onset2_, onset_label)}
-            spec, first, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l, pack = self._vat_two_streams(
-                batch_ul['audio'], audio_label, recon_fn if self.reconstruction else None)
-            r_norm_ul, r_norm_l, r_adv = abs_mean(r_norm_ul), abs_mean(r_norm_l), r_adv.squeeze(1)
-        elif batch_ul:
-            spec = self._front(batch_ul['audio'], audio_label.shape[-1])
-            lds_ul, _, r_norm_ul = self.vat_loss(self, spec)
-            r_norm_ul = abs_mean(r_norm_ul)
-        else:
-            lds_ul = {'frame': torch.tensor(0.), 'onset': torch.tensor(0.)}
-            r_norm_ul = torch.tensor(0.)
-        if not dual:
-            spec = self._front(audio_label, audio_label.shape[-1])
-            first = None
-        if dual:
-            pass
-        elif VAT:
-            first, lds_l, r_adv, r_norm_l = self._vat_reusing_forward(spec)
-            r_adv = r_adv.squeeze(1)
-            r_norm_l = abs_mean(r_norm_l)
-        else:
-            r_adv = None
-            lds_l = {'frame': torch.tensor(0.), 'onset': torch.tensor(0.)}
-            r_norm_l = torch.tensor(0.)
-        tag = 'train' if self.training else 'test'
-        if self.reconstruction and pack is not None:
-            pianoroll, onset, a = first
-            predictions = {'frame': pianoroll, 'onset': onset, 'frame2': pack['frame2'], 'onset2': pack['onset2'], 'attention': a,
-                           'r_adv': r_adv, 'reconstruction': pack['rec']}
-            losses = {
-                f'loss/{tag}_reconstruction': pack['l_rec'],
-                f'loss/{tag}_frame': bce_mean(pianoroll, frame_label),
-                f'loss/{tag}_frame2': pack['l_frame2'],
-                f'loss/{tag}_onset': bce_mean(onset, onset_label),
-                f'loss/{tag}_onset2': pack['l_onset2'],
-            }
-        elif self.reconstruction:
-            reconstrut, pianoroll, onset, pianoroll2, onset2, a = self(spec, first)
-            predictions = {'frame': pianoroll, 'onset': onset, 'frame2': pianoroll2, 'onset2': onset2, 'attention': a,
-                           'r_adv': r_adv, 'reconstruction': reconstrut}
-            if not self.training:
-                predictions['frame'] = pianoroll.reshape(*frame_label.shape)
-                predictions['frame2'] = pianoroll2.reshape(*frame_label.shape)
-            losses = {
-                f'loss/{tag}_reconstruction': mse_mean(reconstrut.squeeze(1), spec.squeeze(1)),
-                f'loss/{tag}_frame': bce_mean(predictions['frame'], frame_label),
-                f'loss/{tag}_frame2': bce_mean(predictions['frame2'], frame_label),
-                f'loss/{tag}_onset': bce_mean(predictions['onset'], onset_label),
-                f'loss/{tag}_onset2': bce_mean(predictions['onset2'], onset_label),
-            }
-        else:
-            frame_pred, onset, a = self(spec, first)
-            predictions = {'onset': onset, 'frame': frame_pred, 'r_adv': r_adv, 'attention': a}
-            if not self.training:
-                predictions['frame'] = frame_pred.reshape(*frame_label.shape)
-            losses = {f'loss/{tag}_frame': bce_mean(predictions['frame'], frame_label),
-                      f'loss/{tag}_onset': bce_mean(predictions['onset'], onset_label)}
-        losses[f'loss/{tag}_LDS_l_frame'] = lds_l['frame']
-        losses[f'loss/{tag}_LDS_l_onset'] = lds_l['onset']
-        if self.training:
-            losses['loss/train_LDS_ul_frame'] = lds_ul['frame']
-            losses['loss/train_LDS_ul_onset'] = lds_ul['onset']
-        losses[f'loss/{tag}_r_norm_l'] = r_norm_l
-        if self.training:
-            losses['loss/train_r_norm_ul'] = r_norm_ul
-        return predictions, losses, spec.squeeze(1)
-
     def transcribe(self, batch):
         """The onset and frame posteriorgrams of ``batch['audio']`` from one transcriber pass (what ``run_on_batch`` in eval mode
         returns under the same keys); the reconstructor does not run."""
@@ -582,6 +583,11 @@ class UNet_Onset(_Base):
 
 
 class UNet(_Base):
+    heads = ('frame',)
+    # the two-stream step of this model runs its reconstruction branch on the main stream after the join (it never passed a
+    # recon_fn): that is the schedule its benchmark numbers were measured with, so changing it is a performance change of its own
+    recon_on_side_stream = False
+
     def __init__(self, ds_ksize, ds_stride, log=True, reconstruction=True, mode='imagewise', spec='CQT', device='cpu',
                  XI=1e-6, eps=1e-2):
         super().__init__(log, reconstruction, mode, spec, XI, eps)
@@ -597,62 +603,6 @@ class UNet(_Base):
             return reconstruction, pianoroll, pianoroll2, a
         return pianoroll, a
 
-    def run_on_batch(self, batch, batch_ul=None, VAT=False):
-        audio_label = batch['audio']
-        frame_label = batch['frame']
-        if frame_label.dim() == 2:
-            frame_label = frame_label.unsqueeze(0)
-        dual = bool(batch_ul) and VAT and self.training and ops.DUAL_STREAM[0] and audio_label.is_cuda
-        if dual:
-            spec, first, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l, _ = self._vat_two_streams(batch_ul['audio'], audio_label)
-            r_norm_ul, r_norm_l, r_adv = abs_mean(r_norm_ul), abs_mean(r_norm_l), r_adv.squeeze(1)
-        elif batch_ul:
-            spec = self._front(batch_ul['audio'], audio_label.shape[-1])
-            lds_ul, _, r_norm_ul = self.vat_loss(self, spec)
-            r_norm_ul = abs_mean(r_norm_ul)
-        else:
-            lds_ul = torch.tensor(0.)
-            r_norm_ul = torch.tensor(0.)
-        if not dual:
-            spec = self._front(audio_label, audio_label.shape[-1])
-            first = None
-        if dual:
-            pass
-        elif VAT:
-            first, lds_l, r_adv, r_norm_l = self._vat_reusing_forward(spec)
-            r_adv = r_adv.squeeze(1)
-            r_norm_l = abs_mean(r_norm_l)
-        else:
-            r_adv = None
-            lds_l = torch.tensor(0.)
-            r_norm_l = torch.tensor(0.)
-        tag = 'train' if self.training else 'test'
-        if self.reconstruction:
-            reconstrut, pianoroll, pianoroll2, a = self(spec, first)
-            if not self.training:
-                pianoroll = pianoroll.reshape(*frame_label.shape)
-                pianoroll2 = pianoroll2.reshape(*frame_label.shape)
-            predictions = {'onset': pianoroll, 'frame': pianoroll, 'frame2': pianoroll2, 'onset2': pianoroll2,
-                           'attention': a, 'r_adv': r_adv, 'reconstruction': reconstrut}
-            losses = {
-                f'loss/{tag}_reconstruction': mse_mean(reconstrut.squeeze(1), spec.squeeze(1)),
-                f'loss/{tag}_frame': bce_mean(predictions['frame'], frame_label),
-                f'loss/{tag}_frame2': bce_mean(predictions['frame2'], frame_label),
-            }
-        else:
-            frame_pred, a = self(spec, first)
-            if not self.training:
-                frame_pred = frame_pred.reshape(*frame_label.shape)
-            predictions = {'onset': frame_pred, 'frame': frame_pred, 'r_adv': r_adv, 'attention': a}
-            losses = {f'loss/{tag}_frame': bce_mean(predictions['frame'], frame_label)}
-        losses[f'loss/{tag}_LDS_l'] = lds_l
-        if self.training:
-            losses['loss/train_LDS_ul'] = lds_ul
-        losses[f'loss/{tag}_r_norm_l'] = r_norm_l
-        if self.training:
-            losses['loss/train_r_norm_ul'] = r_norm_ul
-        return predictions, losses, spec.squeeze(1)
-
     def run_on_batch_application(self, batch, batch_ul=None, VAT=False):
         """model/self_attention_VAT.py:1205-1291: the fine-tuning-on-unlabelled-recordings variant of run_on_batch --
         the unlabelled batch additionally goes through transcriber -> reconstructor -> transcriber and contributes the
@@ -664,47 +614,17 @@ class UNet(_Base):
             raise UnboundLocalError("run_on_batch_application needs batch_ul (model/self_attention_VAT.py:1225 reads `spec` "
                                     'before assignment without it)')
         audio_label = batch['audio']
-        frame_label = batch['frame']
-        if frame_label.dim() == 2:
-            frame_label = frame_label.unsqueeze(0)
+        labels = {'frame': batch['frame'].unsqueeze(0) if batch['frame'].dim() == 2 else batch['frame']}
         spec_ul = self._front(batch_ul['audio'], audio_label.shape[-1])
-        lds_ul, _, r_norm_ul = self.vat_loss(self, spec_ul)
+        plan = StepPlan()
+        plan.lds_ul, _, r_norm_ul = self.vat_loss(self, spec_ul)
         _, ul_pianoroll, ul_pianoroll2, _ = self(spec_ul)
-        spec = self._front(audio_label, audio_label.shape[-1])
-        if VAT:
-            first, lds_l, r_adv, r_norm_l = self._vat_reusing_forward(spec)
-            r_adv = r_adv.squeeze(1)
-            r_norm_l = abs_mean(r_norm_l)
-        else:
-            first, r_adv, lds_l, r_norm_l = None, None, torch.tensor(0.), torch.tensor(0.)
-        reconstrut, pianoroll, pianoroll2, a = self(spec, first)
+        self._labelled_plan(plan, audio_label, VAT)
+        predictions, losses = step_tables(self.heads, self.training, labels, plan, self._branches(plan.spec, plan.first),
+                                          ul=(ul_pianoroll, ul_pianoroll2))
         if self.training:
-            predictions = {'onset': pianoroll, 'frame': pianoroll, 'frame2': pianoroll2, 'onset2': pianoroll2,
-                           'ul_frame': ul_pianoroll, 'ul_frame2': ul_pianoroll2, 'attention': a, 'r_adv': r_adv,
-                           'reconstruction': reconstrut}
-            losses = {
-                'loss/train_reconstruction': mse_mean(reconstrut.squeeze(1), spec.squeeze(1)),
-                'loss/train_frame': bce_mean(pianoroll, frame_label),
-                'loss/train_frame2': bce_mean(pianoroll2, frame_label),
-                'loss/ul_consistency_wrt1': bce_mean(ul_pianoroll2, ul_pianoroll.detach()),
-                'loss/train_LDS_l': lds_l,
-                'loss/train_LDS_ul': lds_ul,
-                'loss/train_r_norm_l': r_norm_l,
-                'loss/train_r_norm_ul': abs_mean(r_norm_ul),
-            }
-        else:
-            pianoroll = pianoroll.reshape(*frame_label.shape)
-            pianoroll2 = pianoroll2.reshape(*frame_label.shape)
-            predictions = {'onset': pianoroll, 'frame': pianoroll, 'frame2': pianoroll2, 'onset2': pianoroll2, 'attention': a,
-                           'r_adv': r_adv, 'reconstruction': reconstrut}
-            losses = {
-                'loss/test_reconstruction': mse_mean(reconstrut.squeeze(1), spec.squeeze(1)),
-                'loss/test_frame': bce_mean(pianoroll, frame_label),
-                'loss/test_frame2': bce_mean(pianoroll2, frame_label),
-                'loss/test_LDS_l': lds_l,
-                'loss/test_r_norm_l': r_norm_l,
-            }
-        return predictions, losses, spec.squeeze(1)
+            losses['loss/train_r_norm_ul'] = abs_mean(r_norm_ul)      # reduced after the table's losses, and not at all in eval mode
+        return predictions, losses, plan.spec.squeeze(1)
 
     def transcribe(self, batch):
         """model/self_attention_VAT.py:1293-1314."""

@@ -18,8 +18,9 @@ import torch.nn as nn
 
 from . import ops
 from .constants import N_BINS
-from .model import _Base, _p
-from .ops import ARENA, BiLstmFn, BnActFn, ConvFn, LinearFn, PoolDropFn, VatPerturbFn, abs_mean, bce_mean
+from .model import StepPlan, _Base, _hand_off, _p, vat_terms
+from .ops import ARENA, BiLstmFn, BnActFn, ConvFn, LinearFn, PoolDropFn, abs_mean, bce_mean, mse_mean
+from .vat import VAT, zero_loss
 
 
 def _conv_bn_relu(conv, bn, x, detach):
@@ -105,41 +106,23 @@ class Combine_Stack(nn.Module):
         return _linear(self.linear, y, 1, detach)
 
 
-class stepwise_VAT(nn.Module):
-    """model/onset_frame_VAT.py:158-207: one power iteration, BCE distance on the frame posteriorgram.  As in
-    reconvat_amd.model.UNet_VAT the weights are detached for the power-iteration pass (the reference discards those
-    gradients with model.zero_grad()), so only the input-gradient chain runs."""
+class stepwise_VAT(VAT):
+    """model/onset_frame_VAT.py:158-207: BCE distance on the frame posteriorgram; returns (loss, r_adv, d_normalised)."""
 
     def __init__(self, XI, epsilon, n_power, KL_Div):
-        super().__init__()
+        super().__init__(XI, epsilon, n_power)
         if KL_Div:
             raise NotImplementedError('only the BCE distance of stepwise_VAT is on the MI355X path (the scripts pass KL_Div=False)')
-        self.n_power, self.XI, self.epsilon, self.KL_Div, self.binwise = n_power, XI, epsilon, KL_Div, False
-        self.nan_flag = None
-        self.noise = None          # optional callable(x) -> d0 (tests inject deterministic noise)
+        self.KL_Div, self.binwise = KL_Div, False
 
-    def forward(self, model, x, check=True):
-        if self.nan_flag is None or self.nan_flag.device != x.device:
-            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        with torch.no_grad():
-            frame_ref = model(x)[2]
-        d = (self.noise(x) if self.noise is not None else torch.randn_like(x)).requires_grad_(True)
-        g = None
-        for it in range(self.n_power):
-            if it > 0:
-                d = (g * 1e10).requires_grad_(True)
-            x_adv = VatPerturbFn.apply(x, d, float(self.XI))
-            loss = bce_mean(model(x_adv, detach=True)[2], frame_ref)
-            g, = torch.autograd.grad(loss, d)
-            g = g.detach()
-        x_adv, r_adv, d_norm = ops.vat_adversarial(x, g, 1e10, float(self.epsilon), self.nan_flag)
-        if check:
-            self.check_nan()
-        return bce_mean(model(x_adv)[2], frame_ref), r_adv, d_norm
+    def outputs(self, model, x, detach=False):
+        return model(x, detach)[2:]
 
-    def check_nan(self):
-        if not torch.cuda.is_current_stream_capturing():
-            assert int(self.nan_flag.item()) == 0, 'r_adv contains nan'
+    def terms(self, preds, refs):
+        return [bce_mean(preds[0], refs[0])]
+
+    def package(self, terms):
+        return terms[0]
 
 
 class OnsetsAndFrames_VAT_full(_Base):
@@ -187,115 +170,90 @@ class OnsetsAndFrames_VAT_full(_Base):
         dev = audio_l.device
         side_ul, side_main = ops.side_stream(dev, 0), ops.side_stream(dev, 1)
         ref_len = audio_l.shape[-1]
+        plan = StepPlan()
         side_ul.wait_stream(cur)
         with torch.cuda.stream(side_ul):
             spec_ul = self._spec(audio_ul, ref_len)
             with ops.deferred_bn_updates() as pend_ul:
-                lds_ul, _, dn_ul = self.vat_loss(self, spec_ul, check=False)
-                r_norm_ul = abs_mean(dn_ul)
-        spec = self._spec(audio_l, ref_len)
+                plan.lds_ul, _, dn_ul = self.vat_loss(self, spec_ul, check=False)
+                plan.r_norm_ul = abs_mean(dn_ul)
+        plan.spec = self._spec(audio_l, ref_len)
         if VAT:
             spec_ready = torch.cuda.Event()
             spec_ready.record(cur)
             with torch.cuda.stream(side_main):
                 side_main.wait_event(spec_ready)
-                spec.record_stream(side_main)
+                _hand_off(side_main, plan.spec)
                 with ops.deferred_bn_updates() as pend_main:
-                    onset_pred, _, frame_pred = self(spec)
+                    onset_pred, _, frame_pred = self(plan.spec)
             with ops.deferred_bn_updates() as pend_l:
-                lds_l, r_adv, dn_l = self.vat_loss(self, spec, check=False)
-                r_norm_l = abs_mean(dn_l)
+                plan.lds_l, plan.r_adv, dn_l = self.vat_loss(self, plan.spec, check=False)
+                plan.r_norm_l = abs_mean(dn_l)
             cur.wait_stream(side_main)
-            for t in (onset_pred, frame_pred):
-                t.record_stream(cur)
+            _hand_off(cur, onset_pred, frame_pred)
             seq = [pend_ul, pend_l, pend_main]
         else:
-            r_adv, lds_l, r_norm_l = None, torch.tensor(0.), torch.tensor(0.)
+            plan.lds_l, plan.r_norm_l = self._no_vat()
             with ops.deferred_bn_updates() as pend_main:
-                onset_pred, _, frame_pred = self(spec)
+                onset_pred, _, frame_pred = self(plan.spec)
             seq = [pend_ul, pend_main]
         cur.wait_stream(side_ul)
-        for t in (lds_ul, r_norm_ul):
-            t.record_stream(cur)
+        _hand_off(cur, plan.lds_ul, plan.r_norm_ul)
         ops.replay_bn_updates(seq, dev)
         self.vat_loss.check_nan()
-        return spec, onset_pred, frame_pred, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l
+        return plan, onset_pred, frame_pred
 
     def run_on_batch(self, batch, batch_ul=None, VAT=False):
-        audio_label = batch['audio']
-        onset_label = batch['onset']
-        frame_label = batch['frame']
+        audio_label, onset_label, frame_label = batch['audio'], batch['onset'], batch['frame']
         if batch_ul and self.training and ops.DUAL_STREAM[0] and audio_label.is_cuda:
-            spec, onset_pred, frame_pred, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l = self._two_streams(
-                batch_ul['audio'], audio_label, VAT)
-            return self._pack(spec, onset_pred, frame_pred, onset_label, frame_label, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l)
-        if batch_ul:
-            spec = self._spec(batch_ul['audio'], audio_label.shape[-1])
-            lds_ul, _, r_norm_ul = self.vat_loss(self, spec)
-            r_norm_ul = abs_mean(r_norm_ul)
+            plan, onset_pred, frame_pred = self._two_streams(batch_ul['audio'], audio_label, VAT)
         else:
-            lds_ul, r_norm_ul = torch.tensor(0.), torch.tensor(0.)
-        spec = self._spec(audio_label, audio_label.shape[-1])
-        if VAT:
-            lds_l, r_adv, r_norm_l = self.vat_loss(self, spec)
-            r_norm_l = abs_mean(r_norm_l)
-        else:
-            r_adv, lds_l, r_norm_l = None, torch.tensor(0.), torch.tensor(0.)
-        onset_pred, _, frame_pred = self(spec)
-        return self._pack(spec, onset_pred, frame_pred, onset_label, frame_label, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l)
-
-    def _pack(self, spec, onset_pred, frame_pred, onset_label, frame_label, lds_ul, r_norm_ul, lds_l, r_adv, r_norm_l):
+            plan = StepPlan()
+            if batch_ul:
+                plan.lds_ul, _, r_norm_ul = self.vat_loss(self, self._spec(batch_ul['audio'], audio_label.shape[-1]))
+                plan.r_norm_ul = abs_mean(r_norm_ul)
+            else:
+                plan.lds_ul, plan.r_norm_ul = self._no_vat()
+            plan.spec = self._spec(audio_label, audio_label.shape[-1])
+            if VAT:
+                plan.lds_l, plan.r_adv, r_norm_l = self.vat_loss(self, plan.spec)
+                plan.r_norm_l = abs_mean(r_norm_l)
+            else:
+                plan.lds_l, plan.r_norm_l = self._no_vat()
+            onset_pred, _, frame_pred = self(plan.spec)
         predictions = {'onset': onset_pred.reshape(*frame_label.shape), 'frame': frame_pred.reshape(*frame_label.shape),
-                       'r_adv': r_adv}
+                       'r_adv': plan.r_adv}
         tag = 'train' if self.training else 'test'
         losses = {f'loss/{tag}_frame': bce_mean(predictions['frame'], frame_label),
-                  f'loss/{tag}_onset': bce_mean(predictions['onset'], onset_label),
-                  f'loss/{tag}_LDS_l': lds_l}
-        if self.training:
-            losses['loss/train_LDS_ul'] = lds_ul
-        losses[f'loss/{tag}_r_norm_l'] = r_norm_l
-        if self.training:
-            losses['loss/train_r_norm_ul'] = r_norm_ul
-        return predictions, losses, spec
+                  f'loss/{tag}_onset': bce_mean(predictions['onset'], onset_label)}
+        return predictions, vat_terms(losses, self.training, plan), plan.spec
 
 
-class stepwise_VAT_frame_stack(nn.Module):
+class stepwise_VAT_frame_stack(VAT):
     """model/onset_frame_VAT.py:209-269: distance = BCE(frame) and / or MSE(activation) by `VAT_mode`, d = d.grad * 1e20;
-    returns (vat_loss, r_adv).  Weights detached for the power-iteration pass (see stepwise_VAT)."""
+    returns (vat_loss, r_adv)."""
+    scale = 1e20
+    nan_message = 'r_adv exploded, please debug tune down the XI for VAT'
 
     def __init__(self, XI, epsilon, n_power, VAT_mode):
-        super().__init__()
+        super().__init__(XI, epsilon, n_power)
         if VAT_mode not in ('activation', 'frame', 'all'):
             raise ValueError(f'VAT_mode {VAT_mode!r}')
-        self.n_power, self.XI, self.epsilon, self.VAT_mode = n_power, XI, epsilon, VAT_mode
-        self.nan_flag = None
-        self.noise = None
+        self.VAT_mode, self.binwise = VAT_mode, False
 
-    def _dist(self, act, frame, act_ref, frame_ref):
-        if self.VAT_mode == 'activation':
-            return ops.mse_mean(act, act_ref)
-        if self.VAT_mode == 'frame':
-            return bce_mean(frame, frame_ref)
-        return bce_mean(frame, frame_ref) + ops.mse_mean(act, act_ref)
+    def outputs(self, model, x, detach=False):
+        return model(x, detach)            # (activation, frame)
 
-    def forward(self, model, x):
-        if self.nan_flag is None or self.nan_flag.device != x.device:
-            self.nan_flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        with torch.no_grad():
-            act_ref, frame_ref = model(x)
-        d = (self.noise(x) if self.noise is not None else torch.randn_like(x)).requires_grad_(True)
-        g = None
-        for it in range(self.n_power):
-            if it > 0:
-                d = (g * 1e20).requires_grad_(True)
-            act, frame = model(VatPerturbFn.apply(x, d, float(self.XI)), detach=True)
-            g, = torch.autograd.grad(self._dist(act, frame, act_ref, frame_ref), d)
-            g = g.detach()
-        x_adv, r_adv, _ = ops.vat_adversarial(x, g, 1e20, float(self.epsilon), self.nan_flag)
-        if not torch.cuda.is_current_stream_capturing():
-            assert int(self.nan_flag.item()) == 0, 'r_adv exploded, please debug tune down the XI for VAT'
-        act, frame = model(x_adv)
-        return self._dist(act, frame, act_ref, frame_ref), r_adv
+    def terms(self, preds, refs):
+        (act, frame), (act_ref, frame_ref) = preds, refs
+        return ([bce_mean(frame, frame_ref)] if self.VAT_mode != 'activation' else []) + \
+               ([mse_mean(act, act_ref)] if self.VAT_mode != 'frame' else [])
+
+    def package(self, terms):
+        return sum(terms[1:], terms[0])
+
+    def forward(self, model, x, refs=None, check=True):
+        return super().forward(model, x, refs, check)[:2]
 
 
 class Frame_stack_VAT(_Base):
@@ -327,11 +285,11 @@ class Frame_stack_VAT(_Base):
             # in the ConvStack's Linear (640 "bins"); there is no behaviour to reproduce
             raise RuntimeError('Frame_stack_VAT.run_on_batch: the unlabelled VAT branch of the reference is not executable '
                                '(shape error at model/onset_frame_VAT.py:466-467); pass batch_ul=None')
-        lds_ul = torch.tensor(0.)
+        lds_ul = zero_loss()
         if VAT:
             lds_l, r_adv = self.vat_loss(self, spec)
         else:
-            r_adv, lds_l = None, torch.tensor(0.)
+            r_adv, lds_l = None, zero_loss()
         _, frame_pred = self(spec)
         predictions = {'onset': frame_pred, 'frame': frame_pred.reshape(*frame_label.shape), 'r_adv': r_adv}
         if self.training:
@@ -370,7 +328,7 @@ class Onset_stack_VAT(_Base):
         onset_pred = self(spec)
         accuracy = (onset_label == (onset_pred.detach() > 0.5)).float().sum() / onset_label.flatten(0).shape[0]
         tag = 'train' if self.training else 'test'
-        lds = torch.tensor(0.)
+        lds = zero_loss()
         losses = {f'loss/{tag}_onset': bce_mean(onset_pred.reshape(*onset_label.shape), onset_label),
                   f'metric/{tag}_accuracy': accuracy,
                   f'loss/{tag}_LDS': torch.mean(torch.stack((lds, lds)), dim=0) if self.training else lds}

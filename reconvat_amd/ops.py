@@ -71,7 +71,7 @@ def bn_ws_doubles(c):
 
 _BN_DEFER = [None]
 
-# Two-stream VAT (model._Base._vat_two_streams).  Off by default: TrainStep switches it on once the weights are packed
+# Two-stream VAT (read by model._Base._step_plan, which then runs _vat_two_streams, and by onset_frames' run_on_batch).  Off by default: TrainStep switches it on once the weights are packed
 # by the one-launch plan and the conv autotuner has run (neither tolerates a concurrent second stream).
 DUAL_STREAM = [False]
 _SIDE = {}

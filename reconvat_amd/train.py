@@ -407,7 +407,7 @@ class TrainStep:
         if self.bf16_backward and os.environ.get('RV_BF16_LOG'):
             import sys
             print('[bf16] backward convs of the final graphs use bf16 operands', file=sys.stderr)
-        self.dual_stream = dual_stream        # the two VAT chains on two HIP streams (model._vat_two_streams)
+        self.dual_stream = dual_stream        # the two VAT chains on two HIP streams (model._Base._step_plan -> _vat_two_streams; onset_frames: _two_streams)
         self._merger = ops.WgradMerger()       # one weight-gradient launch per layer and gradient bucket, not per backward pass
         self._dual_ready = False              # ... from the second step on: the first one packs weights and autotunes
         if getattr(model, 'has_recurrence', False):
