@@ -7,6 +7,7 @@ slice (view) of a wider buffer -- the pixel stride is taken from ``stride(2)``.
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -552,10 +553,45 @@ class BnLink:
         return self.ws is not None and self.z is not None and tuple(self.z.shape) == tuple(dx.shape)
 
 
-def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, s_a, s_b, flip):
+class WgradProblem(namedtuple('WgradProblem', 'mode taps u uld hu wu ca v vld hv wv cb bb s_a s_b flip')):
+    """The pixel-reduction GEMM behind a conv layer's weight gradient (built by _wgrad_geom): G[tap][a][b] = sum_p U[p + tap][a] * V[p][b] over the pixels of
+    the tensors u [bb, hu, wu, ca] and v [bb, hv, wv, cb] (pixel strides uld, vld), scattered to dw[a * s_a + b * s_b + tap] (flip: taps reversed).  The
+    fields are the arguments of rv_conv_wgrad and its deferred / segmented forms; mode 0: 3x3, 1: 1x1, 2: 2x2 stride 2, | 0x100: bf16 operands."""
+    __slots__ = ()
+
+    # what the library keys its partition and its workspace size by (rv_conv_wgrad_set_plan, rv_conv_wgrad_workspace_bytes: no row width) / the tuner and the plan table
+    plan_key = property(lambda self: (self.taps, self.bb, self.hv, self.ca, self.cb))
+    tune_key = property(lambda self: (self.taps, self.bb, self.hv, self.wv, self.ca, self.cb))
+
+    def same_geometry(self, other):
+        """Equal but for where the operands live: the two may be segments of one launch."""
+        return self._replace(u=None, v=None) == other._replace(u=None, v=None)
+
+    def head(self):
+        """The leading arguments of rv_conv_wgrad / rv_conv_wgrad_deferred."""
+        return self.mode, ptr(self.u), self.uld, self.hu, self.wu, self.ca, ptr(self.v), self.vld, self.hv, self.wv, self.cb, self.bb
+
+
+def _wgrad_args(probs, dw, db, ws, nbytes, stream_ptr, acc=None, slot=None):
+    """(entry point, its arguments, the objects the arguments point into) of ONE weight-gradient launch, the only place that knows the four argument
+    lists.  One problem: rv_conv_wgrad; several (of the same geometry): the segmented form.  slot (a reduction-table entry): the deferred form, which
+    always accumulates; else `acc`."""
+    p, n = probs[0], len(probs)
+    if n == 1:
+        head, held = p.head(), None
+    else:
+        held = [(ctypes.c_void_p * n)(*[q.u.data_ptr() for q in probs]), (ctypes.c_void_p * n)(*[q.v.data_ptr() for q in probs])]
+        head = (p.mode, n, ctypes.addressof(held[0]), ctypes.addressof(held[1]), p.uld, p.hu, p.wu, p.ca, p.vld, p.hv, p.wv, p.cb, p.bb)
+    tail = (acc, ptr(ws), nbytes) if slot is None else (ptr(ws), nbytes, slot)
+    name = 'rv_conv_wgrad' + ('' if slot is None else '_deferred') + ('' if n == 1 else '_seg')
+    return name, head + (ptr(dw), p.s_a, p.s_b, p.flip, ptr(db)) + tail + (stream_ptr,), held
+
+
+def _tune_wgrad(lib, p, w):
     """Per-shape partition of the MFMA weight-gradient kernel (waves per workgroup x workgroups on the chip): the plan table's, or the first eager call of a shape
-    times the candidates (scratch outputs) and pins the winner (rv_conv_wgrad_set_plan); under hipGraph capture an untuned shape keeps the library default."""
-    key = (taps, bb, hv, wv, ca, cb)
+    times the candidates (scratch outputs shaped like `w`) and pins the winner (rv_conv_wgrad_set_plan); under hipGraph capture an untuned shape keeps the library default."""
+    key = p.tune_key
+    taps, bb, hv, wv, ca, cb = key
     if not AUTOTUNE or ca * cb * taps <= 144 or ca == 1:
         return
     if AUTOTUNE == 'table' or key in tuning._wgrad_tuned:
@@ -570,11 +606,11 @@ def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, 
     held = []
 
     def try_plan(plan):
-        if lib.rv_conv_wgrad_set_plan(taps, bb, hv, ca, cb, *plan) != 0:
+        if lib.rv_conv_wgrad_set_plan(*p.plan_key, *plan) != 0:
             return 1
-        nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, bb, hv, ca, cb)
+        nbytes = lib.rv_conv_wgrad_workspace_bytes(*p.plan_key)
         ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-        held[:] = [(mode, ptr(u), uld, hu, wu, ca, ptr(v), vld, hv, wv, cb, bb, ptr(dw), s_a, s_b, flip, ptr(db), 0, ptr(ws), nbytes, st.cuda_stream), ws]
+        held[:] = [_wgrad_args([p._replace(mode=p.mode & 0xff)], dw, db, ws, nbytes, st.cuda_stream, acc=0)[1], ws]      # (timed with fp32 operands)
         return lib.rv_conv_wgrad(*held[0])
     choice = tuning.tune('wgrad', key, tuning.wgrad_candidates(taps, hv, winograd=os.environ.get('RV_TUNE_WGRAD_WINO', '1') != '0'), try_plan,
                          lambda plan: tuning.best_of_bursts(lambda: lib.rv_conv_wgrad(*held[0]), st), default=(0, 0),
@@ -583,8 +619,8 @@ def _tune_wgrad(lib, mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, 
     tuning._wgrad_plans[key] = choice
 
 
-def _wgrad_geom(kind, x, dy, w, bf16):
-    """The pixel-reduction GEMM behind a conv layer's weight gradient: (mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, s_a, s_b, flip)."""
+def _wgrad_geom(kind, x, dy, bf16=False):
+    """The WgradProblem of a conv layer's weight gradient.  Pure: shapes and strides in, record out (CPU tensors serve)."""
     bb, h, wd, cin, xld = _geom(x)
     _, ho, wo, cout, yld = _geom(dy)
     if kind == 'up':
@@ -594,119 +630,101 @@ def _wgrad_geom(kind, x, dy, w, bf16):
         v, vld, hv, wv, cb = x, xld, h, wd, cin
         s_a, s_b, flip = 4, cout * 4, 0
     else:
-        mode = {'c3': 0, 't3': 0, 'c1': 1, 'down': 2}[kind]
-        taps = {'c3': 9, 't3': 9, 'c1': 1, 'down': 4}[kind]
+        mode, taps = {'c3': (0, 9), 't3': (0, 9), 'c1': (1, 1), 'down': (2, 4)}[kind]
         u, uld, hu, wu, ca = x, xld, h, wd, cin
         v, vld, hv, wv, cb = dy, yld, ho, wo, cout
-        if kind == 't3':
-            s_a, s_b, flip = cout * 9, 9, 1
-        else:
-            s_a, s_b, flip = taps, cin * taps, 0
+        s_a, s_b, flip = (cout * 9, 9, 1) if kind == 't3' else (taps, cin * taps, 0)
         if bf16 and taps == 9:
             mode |= 0x100                       # bf16 operands on the matrix pipe (opt-in experiment, see BF16)
-    return mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, s_a, s_b, flip
+    return WgradProblem(mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, s_a, s_b, flip)
+
+
+def _wgrad_launch(probs, dw, db, acc, st):
+    """ONE weight-gradient launch on `st`, the current torch stream of dw's device: dw / db (+)= the sum over `probs` -- one WgradProblem, or the same
+    layer's problems of several backward passes as the segments of one launch (those always accumulate).  Inside deferred_wgrad_reductions an
+    accumulating launch only leaves its partial sums and registers the reduction with the stream's table -- unless the sums must be ordered
+    (DETERMINISTIC), and never for the 1 -> many 3x3 layer.  False: the layer has no segmented form, nothing was launched (the caller launches per pass)."""
+    p, n, lib = probs[0], len(probs), _lib.load()
+    if n == 1:
+        _tune_wgrad(lib, p, dw)
+    elif not all(p.same_geometry(q) for q in probs):
+        return False
+    else:
+        p = p._replace(bb=n * p.bb)
+        if AUTOTUNE:
+            # the partition of n * bb images: the table's entry (or the nearest batch's), else the one this process tuned for one pass -- never the
+            # on-line tuner's timing launches (they read n * bb CONTIGUOUS images from the first segment)
+            tuning.wgrad_plan_for(lib, p.tune_key, AUTOTUNE, probs[0].tune_key)
+    nbytes = lib.rv_conv_wgrad_workspace_bytes(*p.plan_key)
+    ws = torch.empty(nbytes // 4, device=dw.device, dtype=torch.float32)
+    tab = None
+    if _WGRAD_DEFER[0] is not None and acc and not DETERMINISTIC[0] and not (p.taps == 9 and p.ca == 1 and p.cb > 16):
+        tab = _WGRAD_DEFER[0].table(st.cuda_stream, lambda: _WgradTable(dw.device, st))
+    name, args, held = _wgrad_args(probs, dw, db, ws, nbytes, st.cuda_stream, acc, None if tab is None else tab.slot())
+    rc = invoke(name, *args)
+    if (rc != 0) if tab is None else (rc <= 0):
+        if n > 1:
+            return False
+        raise RuntimeError(f'{name} failed ({rc}): {_lib.last_error()}')
+    if tab is not None:
+        tab.n += 1
+        tab.keep.append(ws)
+    return True
+
+
+# one backward pass's weight gradient as WgradMerger parks it: dw / db are the buffers it adds into (db None: no bias gradient from this launch), stream the pass's torch stream
+WgradItem = namedtuple('WgradItem', 'kind x dy w dw db bf16 stream')
 
 
 def conv_wgrad(kind, x, dy, w, want_bias=True, dw_acc=None, db_acc=None, bf16=False, colsum=None):
     """(dw, db) in the PyTorch layouts of `w` / bias; with dw_acc/db_acc the results are ADDED into those buffers."""
-    mode, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, s_a, s_b, flip = _wgrad_geom(kind, x, dy, w, bf16)
+    p = _wgrad_geom(kind, x, dy, bf16)
     cout = dy.shape[3]
     acc = 1 if dw_acc is not None else 0
     dw = dw_acc if acc else torch.empty_like(w)
-    if not want_bias:
-        db = None
-    else:
-        db = db_acc if acc else torch.empty(cout, device=w.device, dtype=torch.float32)
-    bias_ptr = None if kind == 'up' else ptr(db)
-    lib = _lib.load()
+    db = None if not want_bias else db_acc if acc else torch.empty(cout, device=w.device, dtype=torch.float32)
+    bias = None if kind == 'up' else db              # (the up-conv's bias gradient is a column sum of dY: below)
+    st = torch.cuda.current_stream(w.device)
     merger = _WGRAD_MERGE[0]
-    if merger is not None and acc and not DETERMINISTIC[0] and ca > 2 and cb > 2 and \
-            merger.submit((_bucket_offset(dw.data_ptr()), mode), (kind, x, dy, w, dw, None if kind == 'up' else db, bf16, torch.cuda.current_stream(w.device))):
-        pass                                       # (launched with the same layer's other passes of this step: WgradMerger)
-    else:
-        _tune_wgrad(lib, mode & 0xff, taps, u, uld, hu, wu, ca, v, vld, hv, wv, cb, bb, w, s_a, s_b, flip)
-        nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, bb, hv, ca, cb)
-        ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-        tables = _WGRAD_DEFER[0]
-        if tables is not None and acc and not DETERMINISTIC[0] and not (taps == 9 and ca == 1 and cb > 16):
-            cur = torch.cuda.current_stream(w.device)
-            tab = tables.get(cur.cuda_stream)
-            if tab is None:
-                tab = tables[cur.cuda_stream] = _WgradTable(w.device, cur)
-            rc = invoke('rv_conv_wgrad_deferred', mode, ptr(u), uld, hu, wu, ca, ptr(v), vld, hv, wv, cb, bb, ptr(dw), s_a, s_b, flip,
-                        bias_ptr, ptr(ws), nbytes, tab.slot(), cur.cuda_stream)
-            if rc <= 0:
-                raise RuntimeError(f'rv_conv_wgrad_deferred failed ({rc}): {_lib.last_error()}')
-            tab.n += 1
-            tab.keep.append(ws)
-        else:
-            call('rv_conv_wgrad', mode, ptr(u), uld, hu, wu, ca, ptr(v), vld, hv, wv, cb, bb, ptr(dw), s_a, s_b, flip,
-                 bias_ptr, acc, ptr(ws), nbytes, stream())
+    if not (merger is not None and acc and not DETERMINISTIC[0] and p.ca > 2 and p.cb > 2 and
+            merger.submit((_bucket_offset(dw.data_ptr()), p.mode), WgradItem(kind, x, dy, w, dw, bias, bf16, st))):
+        _wgrad_launch([p], dw, bias, acc, st)        # (else: launched with the same layer's other passes of this step, WgradMerger)
     if kind == 'up' and want_bias:
         if colsum is not None and colsum.sums is not None:
             # dY's column sums came with the kernel that produced dY (ColsumLink): fold the replicas, no pass over dY
             call('rv_sums_fold', ptr(colsum.sums), colsum.c, 0, cout, ptr(db), acc, stream())
         else:
-            _colsum_into(dy, dy.stride(2), bb * dy.shape[1] * dy.shape[2], cout, db, acc)
+            _colsum_into(dy, dy.stride(2), p.bb * dy.shape[1] * dy.shape[2], cout, db, acc)
     return (None, None) if acc else (dw, db)
-
-
-def _bucket_offset(p_):
-    """A gradient buffer's identity across the chains' gradient buckets (the side chains add into twins of the flat bucket, SIDE_GRADS): its
-    offset inside whichever bucket holds it (no buckets: the pointer itself)."""
-    sg = SIDE_GRADS[0] if (_WGRAD_MERGE_ACROSS and _WGRAD_MERGE_HELPER) else None
-    if sg is None:
-        return p_
-    main, twins = sg
-    for t in (main, *twins.values()):
-        if t.data_ptr() <= p_ < t.data_ptr() + t.numel() * 4:
-            return p_ - t.data_ptr()
-    return p_
-
-
-def _in_main_bucket(p_):
-    sg = SIDE_GRADS[0]
-    return sg is not None and sg[0].data_ptr() <= p_ < sg[0].data_ptr() + sg[0].numel() * 4
 
 
 def conv_wgrad_merged(items):
     """ONE weight-gradient launch for the same layer's (x, dY) pairs of several backward passes (rv_conv_wgrad_seg: up to four segments of
-    identical geometry).  items: [(kind, x, dy, w, dw_acc, db_acc_or_None), ...], all of one layer and one gradient buffer."""
-    kind, x0, dy0, w, dw, db, bf16 = items[0][:7]
-    geo = [_wgrad_geom(it[0], it[1], it[2], w, bf16) for it in items]
-    mode, taps, u0, uld, hu, wu, ca, v0, vld, hv, wv, cb, bb, s_a, s_b, flip = geo[0]
-    same = all(g[0] == mode and g[3:7] == geo[0][3:7] and g[8:] == geo[0][8:] for g in geo)
-    lib = _lib.load()
-    n = len(items)
-    if n == 1 or not same:
-        return False
-    tkey = (taps, n * bb, hv, wv, ca, cb)
-    if AUTOTUNE:
-        # the partition of n * bb images: the table's entry (or the nearest batch's), else the one this process tuned for one pass -- never the
-        # on-line tuner's timing launches (they read n * bb CONTIGUOUS images from the first segment)
-        tuning.wgrad_plan_for(lib, tkey, AUTOTUNE, (taps, bb, hv, wv, ca, cb))
-    nbytes = lib.rv_conv_wgrad_workspace_bytes(taps, n * bb, hv, ca, cb)
-    ws = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    us = (ctypes.c_void_p * n)(*[g[2].data_ptr() for g in geo])
-    vs = (ctypes.c_void_p * n)(*[g[7].data_ptr() for g in geo])
-    tables = _WGRAD_DEFER[0]
-    if tables is not None:
-        cur = torch.cuda.current_stream(w.device)
-        tab = tables.get(cur.cuda_stream)
-        if tab is None:
-            tab = tables[cur.cuda_stream] = _WgradTable(w.device, cur)
-        rc = invoke('rv_conv_wgrad_deferred_seg', mode, n, ctypes.addressof(us), ctypes.addressof(vs), uld, hu, wu, ca, vld, hv, wv, cb, bb,
-                    ptr(dw), s_a, s_b, flip, ptr(db), ptr(ws), nbytes, tab.slot(), cur.cuda_stream)
-        if rc <= 0:
-            return False                           # (no segmented form for this layer: the caller launches per pass)
-        tab.n += 1
-        tab.keep.append(ws)
-    else:
-        rc = invoke('rv_conv_wgrad_seg', mode, n, ctypes.addressof(us), ctypes.addressof(vs), uld, hu, wu, ca, vld, hv, wv, cb, bb,
-                    ptr(dw), s_a, s_b, flip, ptr(db), 1, ptr(ws), nbytes, stream())
-        if rc != 0:
-            return False
-    return True
+    identical geometry).  items: WgradItems (or their tuples), all of one layer and one gradient buffer -- the first one's.  False: not launched."""
+    first = WgradItem(*items[0])
+    probs = [_wgrad_geom(it[0], it[1], it[2], first.bf16) for it in items]
+    return len(probs) > 1 and _wgrad_launch(probs, first.dw, first.db, 1, torch.cuda.current_stream(first.w.device))
+
+
+def _bucket_of(p_):
+    """(is it the main bucket, offset in it) for a gradient pointer inside one of the chains' gradient buckets (the side chains add into twins of the flat
+    bucket, SIDE_GRADS); None outside all of them."""
+    if SIDE_GRADS[0] is not None:
+        main, twins = SIDE_GRADS[0]
+        for t in (main, *twins.values()):
+            if t.data_ptr() <= p_ < t.data_ptr() + t.numel() * 4:
+                return t is main, p_ - t.data_ptr()
+    return None
+
+
+def _bucket_offset(p_):
+    """A gradient buffer's identity across the chains' gradient buckets: its offset inside whichever bucket holds it (no buckets: the pointer itself)."""
+    hit = _bucket_of(p_) if (_WGRAD_MERGE_ACROSS and _WGRAD_MERGE_HELPER) else None
+    return p_ if hit is None else hit[1]
+
+
+def _in_main_bucket(p_):
+    return (_bucket_of(p_) or (False,))[0]
 
 
 # --------------------------------------------------------------------------------------------
@@ -769,14 +787,14 @@ class WgradMerger:
         q = self.pending.pop(key, [])
         if not q:
             return
-        q.sort(key=lambda it: not _in_main_bucket(it[4].data_ptr()))       # the sum goes to the main chain's bucket when one of the passes is its
-        dev = q[0][3].device
+        q.sort(key=lambda it: not _in_main_bucket(it.dw.data_ptr()))       # the sum goes to the main chain's bucket when one of the passes is its
+        dev = q[0].w.device
         cur = torch.cuda.current_stream(dev)
         where = self._helper_for(q) or cur
         # the last pass of the main chain (the main forward's backward) runs while the side chain is idle: its input-gradient chain stays
         # there, the merged weight gradients go next door (they ADD into the main bucket through the reduction table's atomics).  Whatever
         # stream launches: it first waits for every OTHER stream a pass of the group was produced on.
-        origins = {it[7].cuda_stream: it[7] for it in q}
+        origins = {it.stream.cuda_stream: it.stream for it in q}
         with torch.cuda.stream(where):
             for sp, st in origins.items():
                 if sp != where.cuda_stream:
@@ -784,19 +802,15 @@ class WgradMerger:
                     ev.record(st)
                     where.wait_event(ev)
             for it in q:
-                if it[7].cuda_stream != where.cuda_stream:
-                    it[1].record_stream(where)
-                    it[2].record_stream(where)
+                if it.stream.cuda_stream != where.cuda_stream:
+                    it.x.record_stream(where)
+                    it.dy.record_stream(where)
             self._launch_here(q)
 
     def _helper_for(self, q):
-        if not _WGRAD_MERGE_HELPER or len(q) < 2 or not DUAL_STREAM[0] or SIDE_GRADS[0] is None or _WGRAD_DEFER[0] is None:
+        if not _WGRAD_MERGE_HELPER or len(q) < 2 or not DUAL_STREAM[0] or _WGRAD_DEFER[0] is None or not _in_main_bucket(q[0].dw.data_ptr()) or not SIDE_GRADS[0][1]:
             return None
-        main, twins = SIDE_GRADS[0]
-        p_ = q[0][4].data_ptr()
-        if not (main.data_ptr() <= p_ < main.data_ptr() + main.numel() * 4) or not twins:
-            return None
-        dev = q[0][3].device
+        dev = q[0].w.device
         helper = side_stream(dev, 0)
         if helper.cuda_stream == torch.cuda.current_stream(dev).cuda_stream:
             return None
@@ -806,17 +820,17 @@ class WgradMerger:
         # passes of different geometry (the labelled and the unlabelled batch may differ in size) merge among their likes
         groups = {}
         for it in q:
-            groups.setdefault((tuple(it[1].shape), it[1].stride(), tuple(it[2].shape), it[2].stride()), []).append(it)
-        dw0, db0 = q[0][4], q[0][5]                # (every launch of the group adds into the first item's buffers: the main chain's when it has a pass)
+            groups.setdefault((tuple(it.x.shape), it.x.stride(), tuple(it.dy.shape), it.dy.stride()), []).append(it)
+        dw0, db0 = q[0].dw, q[0].db                # (every launch of the group adds into the first item's buffers: the main chain's when it has a pass)
         for g in groups.values():
-            g = [(it[0], it[1], it[2], it[3], dw0, db0 if it[5] is not None else None) + tuple(it[6:]) for it in g]
+            g = [it._replace(dw=dw0, db=db0 if it.db is not None else None) for it in g]
             if len(g) >= 2 and conv_wgrad_merged(g):
                 self.merged_launches += 1
                 continue
             merger, _WGRAD_MERGE[0] = _WGRAD_MERGE[0], None
             try:
-                for kind, x, dy, w, dw, db, bf16, _st in g:   # a single pass, or no segmented form for this layer: per pass after all
-                    conv_wgrad(kind, x, dy, w, db is not None, dw, db, bf16=bf16)
+                for it in g:                           # a single pass, or no segmented form for this layer: per pass after all
+                    conv_wgrad(it.kind, it.x, it.dy, it.w, it.db is not None, it.dw, it.db, bf16=it.bf16)
             finally:
                 _WGRAD_MERGE[0] = merger
 
@@ -874,16 +888,22 @@ class _WgradTable(_HostTable):
 
 
 class _deferred:
-    """Base of the deferred_* contexts: while active, the module's one-element list `slot` exposes the {key: table} dict the launches fill."""
+    """Base of the deferred_* contexts: while active, the module's one-element list `slot` exposes the context, whose {key: table} dict the launches fill."""
 
     def __enter__(self):
         self.prev = self.slot[0]
         self.tables = {}
-        self.slot[0] = self.tables
+        self.slot[0] = self
         return self
 
     def __exit__(self, *exc):
         self.slot[0] = self.prev
+
+    def table(self, key, make):
+        """The table under `key` (a stream, or a stream and more), made on first use."""
+        if key not in self.tables:
+            self.tables[key] = make()
+        return self.tables[key]
 
     def flush(self):
         for t in self.tables.values():
@@ -913,6 +933,44 @@ WGRAD_FIRST = [os.environ.get('RV_WGRAD_FIRST', '1') != '0']
 _WGRAD_FIRST_UPCAT = os.environ.get('RV_WGRAD_FIRST_UPCAT', '1') != '0'      # (the decoder's up-conv + skip-conv pair follows the same order)
 
 
+def _conv_param_grads(kind, x, dy, w, params, need_b, dy_colsum=None, bf16=False):
+    """The weight-gradient half of a conv layer's backward: (dw, db) for autograd, or (None, None) when they were added straight into the .grad of
+    `params` = (weight, bias) -- direct_param_grads, and only when every gradient that is wanted has a buffer there: the weight's, and the bias's unless
+    need_b is False."""
+    gw, gb = _grad_buf(params[0]), _grad_buf(params[1])
+    if gw is None or (gb is None and need_b):
+        gw = gb = None
+    return conv_wgrad(kind, x, dy, w, need_b, gw, gb, bf16=bf16, colsum=dy_colsum)
+
+
+def _conv_input_grad(kind, dy, w, xshape, share=None, bn_in=None, dx_colsum=None, bf16=False):
+    """The input-gradient half: dx, or None when it was added into the GradShare's buffer (a later consumer of a shared input).  bn_in: see
+    conv_dgrad_into (it owns the kernel's epilogue: no GradShare, no column sums then); dx_colsum: a ColsumLink to leave the column sums of dx in."""
+    if share is not None and bn_in is None:
+        return share.dgrad(kind, dy, w, xshape, bf16=bf16)
+    dx = torch.empty(xshape, device=dy.device, dtype=torch.float32)
+    sum_ws = ARENA.take(bn_ws_doubles(xshape[3]), dy.device) if (dx_colsum is not None and bn_in is None) else None
+    conv_dgrad_into(kind, dy, w, dx, bn_in, bf16=bf16, sum_ws=sum_ws)
+    if sum_ws is not None:
+        dx_colsum.sums, dx_colsum.c = sum_ws, xshape[3]
+    return dx
+
+
+def _conv_backward(kind, x, dy, w, params, need_x, need_w, need_b, *, xshape, share=None, bn_in=None, dx_colsum=None, dy_colsum=None, bf16=False,
+                   wgrad_first=None):
+    """One conv layer's backward, (dx, dw, db): its two halves in the order of WGRAD_FIRST (wgrad_first overrides).  dx_colsum is only filled in a
+    final graph (live weights: need_w); dy_colsum (kind 'up': the column sums of dy, the bias gradient) is released afterwards."""
+    dx = dw = db = None
+    for weights in ((True, False) if (WGRAD_FIRST[0] if wgrad_first is None else wgrad_first) else (False, True)):
+        if weights and need_w:
+            dw, db = _conv_param_grads(kind, x, dy, w, params, need_b, dy_colsum, bf16)
+        elif not weights and need_x:
+            dx = _conv_input_grad(kind, dy, w, xshape, share, bn_in, dx_colsum if need_w else None, bf16)
+    if dy_colsum is not None:
+        dy_colsum.sums = None            # drop the reference
+    return dx, dw, db
+
+
 class ConvFn(Function):
     """y = conv(x) for any of the five conv kinds (new contiguous NHWC tensor)."""
 
@@ -938,41 +996,8 @@ class ConvFn(Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = dw = db = None
-        bf = BF16['bwd'] and ctx.live
-
-        def input_grad():
-            nonlocal dx
-            if not ctx.needs_input_grad[0]:
-                return
-            if ctx.share is not None and ctx.bn_in is None:
-                dx = ctx.share.dgrad(ctx.kind, dy, w, ctx.xshape, bf16=bf)
-            else:
-                dx = torch.empty(ctx.xshape, device=dy.device, dtype=torch.float32)
-                sum_ws = None
-                if ctx.dx_colsum is not None and ctx.live and ctx.bn_in is None:
-                    sum_ws = ARENA.take(bn_ws_doubles(ctx.xshape[3]), dy.device)
-                conv_dgrad_into(ctx.kind, dy, w, dx, ctx.bn_in, bf16=bf, sum_ws=sum_ws)
-                if sum_ws is not None:
-                    ctx.dx_colsum.sums, ctx.dx_colsum.c = sum_ws, ctx.xshape[3]
-
-        def weight_grad():
-            nonlocal dw, db
-            if not ctx.needs_input_grad[1]:
-                return
-            pw, pb = ctx.params
-            gw, gb = _grad_buf(pw), _grad_buf(pb)
-            if gw is not None and (gb is not None or not ctx.needs_input_grad[2]):
-                conv_wgrad(ctx.kind, x, dy, w, ctx.needs_input_grad[2], gw, gb, bf16=bf, colsum=ctx.dy_colsum)
-            else:
-                dw, db = conv_wgrad(ctx.kind, x, dy, w, ctx.needs_input_grad[2], bf16=bf, colsum=ctx.dy_colsum)
-        # launch order: see WGRAD_FIRST
-        for part in ((weight_grad, input_grad) if WGRAD_FIRST[0] else (input_grad, weight_grad)):
-            part()
-        if ctx.dy_colsum is not None:
-            ctx.dy_colsum.sums = None            # drop the reference
-        return dx, dw, db, None, None, None, None, None, None, None
+        return _conv_backward(ctx.kind, x, dy.contiguous(), w, ctx.params, *ctx.needs_input_grad[:3], xshape=ctx.xshape, share=ctx.share, bn_in=ctx.bn_in,
+                              dx_colsum=ctx.dx_colsum, dy_colsum=ctx.dy_colsum, bf16=BF16['bwd'] and ctx.live) + (None,) * 7
 
 
 class UpCatFn(Function):
@@ -1005,39 +1030,21 @@ class UpCatFn(Function):
         dcat = dcat.contiguous()
         cu = ctx.cu
         d_up, d_sk = dcat[..., :cu], dcat[..., cu:]
-        dx = ds = dwu = dbu = dws = dbs = None
         pwu, pbu, pws, pbs = ctx.params
-
-        def input_grads():
-            nonlocal dx, ds
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty(ctx.shapes[0], device=dcat.device, dtype=torch.float32)
-                conv_dgrad_into('up', d_up, w_up, dx)
-            if ctx.needs_input_grad[3]:
-                bf = BF16['bwd'] and ctx.live
-                if ctx.share is not None:
-                    ds = ctx.share.dgrad('c3', d_sk, w_skip, ctx.shapes[1], bf16=bf)
-                else:
-                    ds = torch.empty(ctx.shapes[1], device=dcat.device, dtype=torch.float32)
-                    conv_dgrad_into('c3', d_sk, w_skip, ds, bf16=bf)
-
-        def weight_grads():
-            nonlocal dwu, dbu, dws, dbs
-            if ctx.needs_input_grad[1]:
-                gw, gb = _grad_buf(pwu), _grad_buf(pbu)
-                if gw is not None and gb is not None:
-                    conv_wgrad('up', x, d_up, w_up, True, gw, gb, colsum=ctx.dy_colsum)
-                else:
-                    dwu, dbu = conv_wgrad('up', x, d_up, w_up, True, colsum=ctx.dy_colsum)
-            if ctx.needs_input_grad[4]:
-                gw, gb = _grad_buf(pws), _grad_buf(pbs)
-                bfw = BF16['bwd'] and ctx.live
-                if gw is not None and gb is not None:
-                    conv_wgrad('c3', s, d_sk, w_skip, True, gw, gb, bf16=bfw)
-                else:
-                    dws, dbs = conv_wgrad('c3', s, d_sk, w_skip, True, bf16=bfw)
-        for part in ((weight_grads, input_grads) if (WGRAD_FIRST[0] and _WGRAD_FIRST_UPCAT) else (input_grads, weight_grads)):
-            part()
+        need_x, need_wu, _, need_s, need_ws = ctx.needs_input_grad[:5]
+        bf = BF16['bwd'] and ctx.live
+        dx = ds = dwu = dbu = dws = dbs = None
+        # two conv layers, their halves interleaved: BOTH weight gradients (the up conv's with its bias fold first), then both input gradients, or
+        # the reverse.  Both bias gradients are always computed (need_b = True, whatever autograd asks for), so the one direct-gradient rule applies.
+        for weights in ((True, False) if (WGRAD_FIRST[0] and _WGRAD_FIRST_UPCAT) else (False, True)):
+            if weights and need_wu:
+                dwu, dbu = _conv_param_grads('up', x, d_up, w_up, (pwu, pbu), True, ctx.dy_colsum)
+            if weights and need_ws:
+                dws, dbs = _conv_param_grads('c3', s, d_sk, w_skip, (pws, pbs), True, bf16=bf)
+            if not weights and need_x:
+                dx = _conv_input_grad('up', d_up, w_up, ctx.shapes[0])
+            if not weights and need_s:
+                ds = _conv_input_grad('c3', d_sk, w_skip, ctx.shapes[1], ctx.share, bf16=bf)
         if ctx.dy_colsum is not None:
             ctx.dy_colsum.sums = None
         return dx, dwu, dbu, ds, dws, dbs, None, None, None
@@ -1133,28 +1140,7 @@ class BnActFn(Function):
         if ctx.r1:
             # the skip conv's own backward (ConvFn.backward of a 'c1' conv with input x, output gradient dy), launched here: it used to be
             # the first node behind this one on the residual path, so the order of the adds into x's shared gradient is unchanged
-            def r1_input_grad():
-                nonlocal dx1
-                if not ctx.needs_input_grad[11]:
-                    return
-                if ctx.r1_share is not None:
-                    dx1 = ctx.r1_share.dgrad('c1', dy, r1_w, ctx.r1_xshape)
-                else:
-                    dx1 = torch.empty(ctx.r1_xshape, device=dy.device, dtype=torch.float32)
-                    conv_dgrad_into('c1', dy, r1_w, dx1)
-
-            def r1_weight_grad():
-                nonlocal dw1, db1
-                if not ctx.needs_input_grad[12]:
-                    return
-                pw1, pb1 = ctx.r1_params
-                gw1, gb1 = _grad_buf(pw1), _grad_buf(pb1)
-                if gw1 is not None and (gb1 is not None or not ctx.needs_input_grad[13]):
-                    conv_wgrad('c1', r1_x, dy, r1_w, ctx.needs_input_grad[13], gw1, gb1)
-                else:
-                    dw1, db1 = conv_wgrad('c1', r1_x, dy, r1_w, ctx.needs_input_grad[13])
-            for part in ((r1_weight_grad, r1_input_grad) if WGRAD_FIRST[0] else (r1_input_grad, r1_weight_grad)):
-                part()
+            dx1, dw1, db1 = _conv_backward('c1', r1_x, dy, r1_w, ctx.r1_params, *ctx.needs_input_grad[11:14], xshape=ctx.r1_xshape, share=ctx.r1_share)
         bb, h, wd, c, zld = _geom(z)
         p = bb * h * wd
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
@@ -1299,18 +1285,14 @@ _TABLE_PARK = os.environ.get('RV_GEMM_TABLE_PARK', '1') != '0'      # (0: every 
 
 def _defer_gemm(a, b_kn, c, splitk, batch, bstrides, a_rowsum):
     """Register c += a @ b_kn (atomic split-K) with the active deferred_param_gemms context; False if none is active."""
-    tables = _GEMM_DEFER[0]
-    if tables is None:
+    if _GEMM_DEFER[0] is None:
         return False
     pa, m, k, sam, sak = _mat(a)
     pb, _, n, sbk, sbn = _mat(b_kn)
     pc, _, _, scm, scn = _mat(c)
     cur = torch.cuda.current_stream(c.device)
     orient = (1 if sak <= sam else 0) | (2 if sbk <= sbn else 0)
-    key = (cur.cuda_stream, orient)
-    tab = tables.get(key)
-    if tab is None:
-        tab = tables[key] = _GemmTable(c.device, cur, orient)
+    tab = _GEMM_DEFER[0].table((cur.cuda_stream, orient), lambda: _GemmTable(c.device, cur, orient))
     if tab.n >= tab.capacity:
         return False
     lib = _lib.load()

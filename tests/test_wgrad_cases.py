@@ -188,7 +188,8 @@ def _scatter(G, s_a, s_b, flip, size):
 
 @pytest.mark.parametrize('kind', ['c3', 't3', 'c1', 'down', 'up'])
 def test_reference_against_torch_autograd(kind):
-    """the five layer kinds with the (mode, U, V, s_a, s_b, flip) ops._wgrad_geom passes"""
+    """the five layer kinds with the (mode, U, V, s_a, s_b, flip) ops._wgrad_geom passes (the function itself, on the CPU tensors)"""
+    from reconvat_amd import ops
     g = torch.Generator().manual_seed(5)
     B, H, W, cin, cout = 2, 5, 7, 3, 4
     x = torch.randn(B, cin, H, W, generator=g, dtype=torch.float64)
@@ -200,12 +201,10 @@ def test_reference_against_torch_autograd(kind):
     dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     (y * dy).sum().backward()
     xn, dyn = x.permute(0, 2, 3, 1).contiguous(), dy.permute(0, 2, 3, 1).contiguous()
-    if kind == 'up':
-        mode, Uu, Vv, (s_a, s_b, flip) = 2, dyn, xn, (4, cout * 4, 0)
-    else:
-        mode, Uu, Vv = {'c3': 0, 't3': 0, 'c1': 1, 'down': 2}[kind], xn, dyn
-        taps = wc.TAPS[mode]
-        s_a, s_b, flip = (cout * 9, 9, 1) if kind == 't3' else (taps, cin * taps, 0)
+    p = ops._wgrad_geom(kind, xn, dyn)
+    mode, Uu, Vv, s_a, s_b, flip = p.mode, p.u, p.v, p.s_a, p.s_b, p.flip
+    assert p.taps == wc.TAPS[mode] and (Uu is dyn and Vv is xn if kind == 'up' else Uu is xn and Vv is dyn)
+    assert (p.bb, p.hu, p.wu, p.ca, p.uld) == (*Uu.shape, Uu.shape[3]) and (p.bb, p.hv, p.wv, p.cb, p.vld) == (*Vv.shape, Vv.shape[3])
     G, db, N = wc.wgrad_ref(mode, Uu, Vv)
     got = _scatter(G, s_a, s_b, flip, layer.weight.numel())
     assert torch.allclose(got, layer.weight.grad.reshape(-1), rtol=1e-12, atol=1e-12)

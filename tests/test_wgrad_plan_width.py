@@ -27,7 +27,7 @@ def fresh(monkeypatch):
 
 
 def launch(lib, taps, bb, hv, wv, ca, cb):
-    ops._tune_wgrad(lib, 0, taps, None, 0, hv, wv, ca, None, 0, hv, wv, cb, bb, None, 0, 0, 0)
+    ops._tune_wgrad(lib, ops.WgradProblem(0, taps, None, 0, hv, wv, ca, None, 0, hv, wv, cb, bb, 0, 0, 0), None)
 
 
 def _mel_key_with_plan():

@@ -7,10 +7,11 @@ layer (model.py / onset_frames.py / vat.py / train.py) that must change neither.
 For every configuration at the fixture shape of the goldens (B = 2, T = 64, oracle.fixture parameters, batches and injected
 noise) it records the raw bits of every loss, SHA-256 of every prediction, of every BatchNorm running statistic and
 `num_batches_tracked` and -- with --deterministic (ops.DETERMINISTIC: no fp32 atomics in the parameter gradients) -- of every
-`param.grad`, and the ordered list of library entry points with the stream each was launched on (through `_lib.HOOK`).
+`param.grad`, and the ordered list of library entry points with the stream each was launched on and a hash of its arguments -- every
+non-pointer value, and which pointers are NULL -- (through `_lib.HOOK`).
 `--package-root` names the directory that holds the `reconvat_amd` package to import (default: this checkout), e.g. the parent
 exported by `git archive <parent> | tar -x -C <dir>` (or a `git worktree`) with this checkout's `libreconvat_hip.so` copied next to
-its sources, so that both runs load the same library.  Result of the last use: profiles/step_plan_ab.txt.
+its sources, so that both runs load the same library.  Results: profiles/step_plan_ab.txt, profiles/conv_backward_ab.txt.
 """
 import argparse
 import hashlib
@@ -61,7 +62,11 @@ def main():
     launches = []
 
     def hook(name, a, fn):
-        launches.append((name, torch.cuda.current_stream().cuda_stream))
+        # the arguments as far as they repeat from run to run: every non-pointer value (pointers vary with allocation: only whether one is NULL)
+        types = _lib.SIGNATURES[name][1]
+        assert len(a) == len(types), name
+        what = repr([(v is not None and v != 0) if t is _lib.P else v for v, t in zip(a, types)])
+        launches.append((name, torch.cuda.current_stream().cuda_stream, hashlib.sha256(what.encode()).hexdigest()[:16]))
         return fn(*a)
 
     def batch(tag, T=64):
@@ -93,7 +98,7 @@ def main():
         rec = {'losses': {k: bits(v) for k, v in losses.items()},
                'predictions': {k: None if v is None else sha(v) for k, v in preds.items()},
                'bn': {k: sha(v) for k, v in m.state_dict().items() if k.endswith(('running_mean', 'running_var', 'num_batches_tracked'))},
-               'launches': [[n, 'main' if s == main else sides.get(s, 'other')] for n, s in launches]}
+               'launches': [[n, 'main' if s == main else sides.get(s, 'other'), h] for n, s, h in launches]}
         if args.deterministic:
             rec['grads'] = grads
         return rec
