@@ -6,7 +6,9 @@ What conv_fwd_impl, launch_conv_rt, choose_tiles, pack_args_make, rv_packed_weig
 decide on the host or per workgroup is restated here in Python (`conv_regime`, `packed_weight_floats`, `pack_mirror`), and every
 case below carries the regime it is meant to reach.  tests/test_conv_cases.py asserts on the CPU that each case lands in its regime,
 that the cases together reach every regime and every template instantiation, that torch's float32 CPU convolution meets the derived
-bound and that emulated kernel faults miss it; tests/test_conv_regimes_gpu.py runs the kernels through the C ABI.
+bound and that emulated kernel faults miss it; tests/test_conv_regimes_gpu.py runs the kernels through the C ABI.  The persistent 3x3 band kernel
+has its launch arithmetic and case table in tests/band_cases.py: `conv_regime` hands its calls over, and `reference` rounds the operands to bf16
+where that regime says so.
 
 Detection is by construction, as in tests/gemm_cases.py.  Every case runs two problems:
   * the INTEGER problem: inputs, weights, bias and start values from {+-1, +-2, +-3}; every partial sum is an integer below 2^24, so
@@ -185,9 +187,12 @@ def conv_regime(mode, B, H, W, Cin, Ho, Wo, Cout, in_ld=None, out_ld=None, algo=
     nchunk, npix = Cin // (4 * R), B * Ph * Pw
     ntiles = cdiv(npix, 16)
     fam, f_nt, f_mt = (algo >> 8) & 15, (algo >> 4) & 15, algo & 15
+    if mode == 0 and algo & ~(1 << 20) != 1 and fam not in (1, 5):   # the persistent 3x3 band kernel: tests/band_cases.py
+        import band_cases
+        return band_cases.band_regime(B, H, W, Cin, Cout, in_ld=in_ld, out_ld=out_ld, algo=algo, bias=bias, accumulate=accumulate, stats=stats, z_ld=z_ld,
+                                      in_off=in_off, out_off=out_off)
+    algo &= ~(1 << 20)                                               # bf16 operands: ignored outside the band kernel
     assert fam in (0, 1, 5), 'only the direct kernel is mirrored'
-    if mode == 0 and algo != 1 and fam not in (1, 5):
-        return dict(reg, kernel='lds3x3')                            # (out of scope here)
     NT, MT, score = choose_tiles(ntiles, ntile_n)
     nsteps = KH * KW * nchunk
     ks = fam == 5
@@ -380,7 +385,7 @@ def case_regime(case, algo=None):
     c = case
     return conv_regime(c['mode'], c['B'], c['H'], c['W'], c['cin'], c['Ho'], c['Wo'], c['cout'], in_ld=c['cin'] + c['in_pad'], out_ld=c['cout'] + c['out_pad'],
                        algo=c['algo'] if algo is None else algo, bias=c['bias'], accumulate=c['acc'], stats=c['stats'], z_ld=c['cout'] + c['z_pad'],
-                       bias_off=c['bias_off'], in_off=c['in_off'], z_off=c['z_off'], coef_off=c['coef_off'])
+                       bias_off=c['bias_off'], in_off=c['in_off'], z_off=c['z_off'], coef_off=c['coef_off'], out_off=c.get('out_off', 0))
 
 
 # 1. the direct MFMA kernel with forced tiles 0x1NM -------------------------------------------------------------------------------
@@ -665,10 +670,10 @@ def problem(case, kind):
         pr['bias_at'] = GUARD + c['bias_off']
         pr['bias_buf'] = _nan_buffer(GUARD + c['bias_off'] + cout + GUARD)
         pr['bias_buf'][pr['bias_at']:pr['bias_at'] + cout] = pr['bias']
-    pr['out_at'] = GUARD
-    pr['out_buf'] = _pad_buffer(GUARD + B * Ho * Wo * pr['out_ld'] + GUARD)
+    pr['out_at'] = GUARD + c.get('out_off', 0)                       # (out_off: the band cases of tests/band_cases.py)
+    pr['out_buf'] = _pad_buffer(pr['out_at'] + B * Ho * Wo * pr['out_ld'] + GUARD)
     if c['acc']:
-        nhwc_view(pr['out_buf'], GUARD, B, Ho, Wo, cout, pr['out_ld']).copy_(pr['out0'])
+        nhwc_view(pr['out_buf'], pr['out_at'], B, Ho, Wo, cout, pr['out_ld']).copy_(pr['out0'])
     if c['stats'] == 'z':
         # z, and coef = [mean | invstd | scale | shift | var]: |z * scale| >= 0.25 and |shift| <= 0.1, so z * scale + shift stays 0.15 away from the kink
         gz = _gen(c['seed'], 77)
@@ -709,6 +714,11 @@ def padding_intact(pr, buf):
 _refs = {}
 
 
+def bf16_round(t):
+    """float32 -> the nearest bf16 number (ties to even) as float32: v_cvt_pk_bf16_f32"""
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
 def reference(pr):
     """-> {'out': float64 [B, Ho, Wo, Cout] (the integer problem: computed in int64), 'bound': per element, 'mag'}"""
     key = (pr['case']['name'], pr['kind'])
@@ -718,12 +728,15 @@ def reference(pr):
     reg = case_regime(c)
     dt = torch.int64 if pr['kind'] == 'int' else torch.float64
     bias = None if pr['bias'] is None else pr['bias'].to(dt)
-    out = conv_ref(c['mode'], pr['x'].to(dt), pr['Wm'].to(dt), bias, c['Ho'], c['Wo'], c['cout']).double()
-    mag = conv_ref(c['mode'], pr['x'].double().abs(), pr['Wm'].double().abs(), None if bias is None else pr['bias'].double().abs(), c['Ho'], c['Wo'], c['cout'])
+    # bf16 operands (the band kernel under bit 20): the reference rounds x and w first, and 2K stands for K (a full ulp for each internal add of the matrix pipe)
+    bf = bool(reg.get('bf'))
+    x, Wm = (bf16_round(pr['x']), bf16_round(pr['Wm'])) if bf else (pr['x'], pr['Wm'])
+    out = conv_ref(c['mode'], x.to(dt), Wm.to(dt), bias, c['Ho'], c['Wo'], c['cout']).double()
+    mag = conv_ref(c['mode'], x.double().abs(), Wm.double().abs(), None if bias is None else pr['bias'].double().abs(), c['Ho'], c['Wo'], c['cout'])
     if c['acc']:
         out = out + pr['out0'].double()
         mag = mag + pr['out0'].double().abs()
-    ref = {'out': out, 'mag': mag, 'bound': 1.01 * (reg['K'] + reg['f'] + 3) * U * mag}
+    ref = {'out': out, 'mag': mag, 'bound': 1.01 * ((2 if bf else 1) * reg['K'] + reg['f'] + 3) * U * mag}
     _refs[key] = ref
     return ref
 
@@ -750,15 +763,19 @@ def compare(pr, out):
 def stats_reference(pr, out):
     """float64 sums of the device's own `out` as read back -> (sums [2, C], sum |term| [2, C]).  forward kind: (sum y, sum y^2); bn_z kind: (sum dd,
     sum dd * xhat) with dd = out * lrelu'(z * scale + shift), xhat = (z - mean) * invstd"""
+    t1, t2 = stats_terms(pr, out)
+    return torch.stack([t1.sum(0), t2.sum(0)]), torch.stack([t1.abs().sum(0), t2.abs().sum(0)])
+
+
+def stats_terms(pr, out):
+    """the two float64 terms [pixels, C] a pixel adds to the statistics of its channels"""
     c = pr['case']
     y = out.detach().double().cpu().reshape(-1, c['cout'])
     if c['stats'] == 'z':
         z, coef = pr['z'].double().reshape(-1, c['cout']), pr['coef'].double()
         dd = torch.where(z * coef[2] + coef[3] > 0, y, y * float(torch.tensor(c['slope'], dtype=torch.float32)))
-        t1, t2 = dd, dd * (z - coef[0]) * coef[1]
-    else:
-        t1, t2 = y, y * y
-    return torch.stack([t1.sum(0), t2.sum(0)]), torch.stack([t1.abs().sum(0), t2.abs().sum(0)])
+        return dd, dd * (z - coef[0]) * coef[1]
+    return y, y * y
 
 
 def stats_ratio(pr, out, sums_buf, exact=None):
