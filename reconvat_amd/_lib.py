@@ -92,6 +92,7 @@ SIGNATURES = {
     'rv_eval_note_velocity': (I, [P, P, L, F, P, L, P, L, P]),
     'rv_hmm_workspace_bytes': (L, [L, I]),
     'rv_hmm_decode': (I, [P, P, L, P, P, I, P, P, P, L, P]),
+    'rv_onset_refine': (I, [P, L, P, P, L, I, P, P, P]),
     'rv_lstm_flag_bytes': (L, [I]),
     'rv_lstm_fwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     'rv_lstm_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P]),

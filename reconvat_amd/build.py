@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libreconvat_hip.so')
-SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip', 'gemm.hip', 'attn.hip', 'elementwise.hip', 'mel.hip', 'cqt.hip', 'thickstun.hip', 'data.hip', 'acoustics.hip', 'resample.hip', 'synth.hip', 'align.hip', 'eval.hip', 'velocity.hip', 'hmm.hip', 'lstm.hip', 'api.cpp']
+SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip', 'gemm.hip', 'attn.hip', 'elementwise.hip', 'mel.hip', 'cqt.hip', 'thickstun.hip', 'data.hip', 'acoustics.hip', 'resample.hip', 'synth.hip', 'align.hip', 'eval.hip', 'velocity.hip', 'hmm.hip', 'onset_time.hip', 'lstm.hip', 'api.cpp']
 # the sources whose host code changes with the variant (RV_KNOB / RV_LAB / RV_ABLATION; tests/test_abi.py checks the list): a variant
 # compiles these and LAB_SOURCES to objects of its own and shares every other object with the product
 VARIANT_SOURCES = ['conv.hip', 'conv_wino2.hip', 'bn.hip']

@@ -441,6 +441,52 @@ def evaluate_with_velocity(data, model, head, onset_threshold=0.5, frame_thresho
 
 
 # ---------------------------------------------------------------------------------------------
+# onset timing against exact note lists
+# ---------------------------------------------------------------------------------------------
+TIMING_TOLERANCES = ((0.05, '50ms'), (0.01, '10ms'))
+
+
+def evaluate_timing(data, model, decoder=None, refine=False, lead=0, device_metrics=False):
+    """How close the transcribed onsets are to the EXACT onsets of a corpus that carries its note lists (``RenderedScores.scores``: tsv
+    rows in seconds) -- ``evaluate_wo_velocity`` decodes its reference from the label roll and cannot see anything finer than a frame.
+    One eval-mode ``run_on_batch`` per whole track (``_songs``), the notes of ``decoder`` (a ``NoteDecoder``, default rule2 at 0.5 / 0.5)
+    and, with ``refine``, their onsets moved by ``onset_time.refine_intervals(..., lead)`` on the track's audio where it is (the kernel on
+    a HIP device).  Per song: ``metric/timing/{precision,recall,f1}@50ms`` and ``@10ms`` (``evaluate_notes`` against the exact rows,
+    onsets only) and ``metric/timing/onset_error_{mean,median}_ms`` over the pairs matched at 50 ms (0 without a pair).
+    ``device_metrics`` picks the device decoder and ``match_notes_sparse``: same values.  ValueError for a dataset without ``scores`` or
+    one that crops its tracks."""
+    from . import onset_time
+    scores = getattr(data, 'scores', None)
+    if scores is None or len(scores) != len(data):
+        raise ValueError('evaluate_timing needs a dataset with exact note lists: RenderedScores and its `scores`')
+    if getattr(data, 'sequence_length', None) is not None:
+        raise ValueError('evaluate_timing works on whole tracks (sequence_length=None): the note lists count from the first sample')
+    decoder = NoteDecoder(rule='rule2') if decoder is None else decoder
+    lead = onset_time._lead(lead)
+    matcher = match_notes_sparse if device_metrics else match_notes
+    metrics = defaultdict(list)
+    for rows, song in zip(scores, _songs(data, model, True, False, False, device_metrics)):
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+        p_ref, i_ref = midi_to_hz(rows[:, 2]), rows[:, :2]
+        pitches, intervals, _, _ = decoder(song.est_on, song.pred['frame'], None, device_metrics)
+        if refine:
+            audio = song.label['audio'].reshape(-1)
+            i_est = onset_time.refine_intervals(audio, pitches, intervals, lead, device=audio.is_cuda)
+            p_est = _to_eval_units(pitches, intervals)[0]
+        else:
+            p_est, i_est = _to_eval_units(pitches, intervals)
+        for tol, tag in TIMING_TOLERANCES:
+            p, r, f, _ = evaluate_notes(i_ref, p_ref, i_est, p_est, onset_tolerance=tol, offset_ratio=None, match=matcher)
+            for k, v in zip(('precision', 'recall', 'f1'), (p, r, f)):
+                metrics[f'metric/timing/{k}@{tag}'].append(v)
+        pairs = matcher(i_ref, p_ref, i_est, p_est, 0.05, 50.0, None, 0.05) if len(p_ref) and len(p_est) else []
+        err = np.array([abs(i_est[j, 0] - i_ref[i, 0]) for i, j in pairs]) * 1e3
+        metrics['metric/timing/onset_error_mean_ms'].append(float(err.mean()) if len(err) else 0.0)
+        metrics['metric/timing/onset_error_median_ms'].append(float(np.median(err)) if len(err) else 0.0)
+    return metrics
+
+
+# ---------------------------------------------------------------------------------------------
 # decoding thresholds chosen on a validation set (DESIGN 3.10)
 # ---------------------------------------------------------------------------------------------
 SWEEP_KEYS = ('n_est', 'matched', 'matched_with_offsets', 'frame_tp', 'frame_est')      # int64 [n_on, n_fr] each; order of rv_eval_sweep

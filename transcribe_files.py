@@ -18,6 +18,9 @@ MIDI file and in the rendering.  Without it every note has velocity 127, as befo
 tables come from ``onset_threshold=`` / ``frame_threshold=``, ``note_on=`` / ``note_off=`` / ``restrike=`` (default 2.0 nats each) are
 the costs of switching -- tune_hmm.py chooses all five on the validation split -- and the onset roll counts as evidence iff the
 checkpoint has an onset head.  ``min_frames=`` / ``bridge_gap=`` and ``velocity=`` work on its notes as on the threshold decoder's.
+``refine_onsets=True`` moves every decoded onset off the 32 ms frame grid to the sample at which the note's own harmonics rise most
+steeply in the audio (after either decoder and after clean-up); ``onset_lead=<samples>`` (default 0) places it that much
+earlier, for voices with a slow attack.  Without it the onsets are frame times, as before.
 
 Inputs: ``.wav`` files of any sample rate and channel count (16 / 24 / 32-bit PCM or float; anything but 16 kHz 16-bit is
 resampled to 16 kHz mono on the model's device) or ``.pt`` track caches (dict with an int16 ``audio`` tensor).
@@ -68,10 +71,14 @@ def write_rendering(path, notes, n_samples, device):
 
 
 def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_threshold=0.5, rule='rule2', tag='ReconVAT', min_frames=1,
-                    bridge_gap=0, render=False, head=None, hmm=None):
+                    bridge_gap=0, render=False, head=None, hmm=None, refine_onsets=False, onset_lead=0):
     """``hmm``: a ``reconvat_amd.NoteHMM``.  The notes are then those of its Viterbi path (the two thresholds are unused:
     the model carries its own), found where the posteriorgrams are; the path's ONSET roll and ONSET-or-SUSTAIN roll take the place of
-    the posteriorgrams in everything after the decode, so a note's velocity is the mean over its ONSET frames."""
+    the posteriorgrams in everything after the decode, so a note's velocity is the mean over its ONSET frames.
+    ``refine_onsets``: the decoded notes (either decoder, after clean-up) go through ``onset_time.refine_intervals`` on the audio, where it
+    is: onsets at the sample of steepest harmonic rise, ``onset_lead`` samples earlier, in place of the 32 ms frame grid."""
+    from reconvat_amd import onset_time
+    onset_lead = onset_time._lead(onset_lead)
     decode = NoteDecoder(onset_threshold, frame_threshold, rule, min_frames, bridge_gap, hmm)
     os.makedirs(out_dir, exist_ok=True)
     for path in files:
@@ -85,7 +92,10 @@ def transcribe2midi(files, model, device, out_dir, onset_threshold=0.5, frame_th
         p_est, i_est, v_est, _ = decode(onset, frame, roll, device=frame.is_cuda)
         midi_vel = None if v_est is None else velocity.midi_velocities(v_est)
         scaling = HOP_LENGTH / SAMPLE_RATE
-        i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
+        if refine_onsets:                       # sub-frame onsets from the audio itself (csrc/onset_time.hip on a HIP device)
+            i_est = onset_time.refine_intervals(audio, p_est, i_est, onset_lead, device=audio.is_cuda)
+        else:
+            i_est = (np.asarray(i_est) * scaling).reshape(-1, 2)
         keys = MIN_MIDI + np.asarray(p_est, dtype=np.float64).reshape(-1)
         p_est = np.array([midi_to_hz(MIN_MIDI + m) for m in p_est])
         midi_path = os.path.join(out_dir, tag + '-' + os.path.splitext(os.path.basename(path))[0] + '.mid')
@@ -132,7 +142,7 @@ def main(argv):
         raise SystemExit(f"decoder must be 'threshold' or 'hmm', got {cfg['decoder']!r}")
     model = load_model(cfg['weight'], cfg['spec'], cfg['device'])
     files = sorted(os.path.join(cfg['input'], f) for f in os.listdir(cfg['input']) if f.endswith(('.wav', '.pt')))
-    cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap', 'render') if k in given}        # handed on only when given
+    cleanup = {k: given[k] for k in ('min_frames', 'bridge_gap', 'render', 'refine_onsets', 'onset_lead') if k in given}     # handed on only when given
     if cfg['velocity']:
         cleanup['head'] = load_head(cfg['velocity'], model, cfg['device'])
     if cfg['decoder'] == 'hmm':                 # the tables come from the two thresholds; onsets count iff the checkpoint has an onset head
